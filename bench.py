@@ -7,17 +7,24 @@ classify, parse + weights, first-touch node ids, node-name blob, triplets and (d
 the A.maximum(A.T) symmetrisation.  The gzip inflate and the PCIe copy are host ingest,
 measured separately (the end_to_end leg).
 
+A plain run sets up, warms up, times `--steps` steps and prints the line; every other leg
+(alt_paths, other_configs, scaling_reference, cpu_baseline, end_to_end; sharded runs: one_gpu and
+the hashed-names leg) runs after the timed steps under `--full` only.  `--dump-outputs DIR` writes
+what the last timed step returned as DIR/<name>.npy (dump_result), the same for the same arguments
+(one-GPU device-resident builds; sharded runs, whose slices stay with their ranks, refuse it).
+
 * `--gpus 1` (default): C4 of BASELINE.json (50M S / 200M L, default flags), the north star's
-  200M-edge config, is `value`.  The same line carries `scaling_reference`: C5 (the multi-GPU
-  config) built by one GPU alone and through the sharded protocol at one rank, with decimal and
-  hashed segment names — the first point of the N-GPU curve on the N-GPU workload.
+  200M-edge config, is `value`.  With `--full` the same line carries `scaling_reference`: C5 (the
+  multi-GPU config) built by one GPU alone and through the sharded protocol at one rank, with decimal
+  and hashed segment names — the first point of the N-GPU curve on the N-GPU workload.
 * `--gpus N > 1`: C5 as ONE file byte-range-sharded over N ranks (strong scaling: the total work
   is fixed), one process per GPU over RCCL.  Under `torch.distributed.run` the ranks come from its
   environment; started plainly (`python bench.py --gpus N`, no WORLD_SIZE) the script launches the
   N rank processes itself before anything touches a GPU.  Every rank checks that the process group
   holds exactly N ranks on the nccl backend and exits non-zero otherwise.  `value` = the file's
-  edge records / max-over-ranks time (decimal names: the fast path); `alt_paths.hashed_names` times
-  the general owner protocol on the same dimensions with hashed names.
+  edge records / max-over-ranks time (decimal names: the fast path); with `--full`, `one_gpu` is the
+  same file built by rank 0's GPU alone and `alt_paths.hashed_names` times the general owner protocol
+  on the same dimensions with hashed names.
 
 Prints ONE JSON line on rank 0.
 """
@@ -45,6 +52,13 @@ def _args():
     ap.add_argument("--workload", default=None, choices=["C2", "C3", "C4", "C5"],
                     help="default: C4 on one GPU (the headline config), C5 byte-range-sharded over N > 1 ranks")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debug only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also every other leg: alt_paths, other_configs, the C5 "
+                         "scaling_reference, cpu_baseline, end_to_end (sharded runs: one_gpu and the hashed-names "
+                         "leg); the --no-* options below drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the CSR and the node names; a fixed sample "
+                         "of each array above DUMP_SAMPLE elements) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-links", type=int, default=12_000_000)
     ap.add_argument("--phases", action="store_true", help="print per-phase ms to stderr")
@@ -64,7 +78,10 @@ def _args():
     ap.add_argument("--shard", action="store_true",
                     help="byte-range-shard the workload's one file over the ranks (gfa2network_amd/shard.py; "
                          "always on for C5)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the line
+        args.no_cpu_baseline = args.no_e2e = args.no_alt = args.no_c5_reference = True
+    return args
 
 
 def _free_port() -> int:
@@ -168,6 +185,58 @@ def _max_over_ranks(world, value: float) -> float:
 def algorithmic_bytes(input_bytes: int, n_nodes: int, nnz: int, w_dtype: int, w_idx: int = 4) -> int:
     """B_alg = B_in + (n+1) w_idx + nnz (w_idx + w_dtype)."""
     return input_bytes + (n_nodes + 1) * w_idx + nnz * (w_idx + w_dtype)
+
+
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: elements kept of an output array that holds more
+DUMP_RUN = 1 << 12     # ... taken as runs of this many consecutive elements
+
+
+def dump_array(out_dir: str, name: str, ptr: int, count: int, dtype, seed: int = 0) -> None:
+    """--dump-outputs: the `count` elements of `dtype` at device pointer `ptr` as out_dir/<name>.npy.
+    Integers are written as float64 (exact below 2^53), bytes as float32, floats in their own
+    width.  An array above DUMP_SAMPLE elements is sampled: its first and its last DUMP_RUN elements
+    and runs of DUMP_RUN at offsets drawn from numpy's PCG64 seeded with `seed` — the same elements
+    for the same count in every run, 8 MiB per array at the most."""
+    import numpy as np
+
+    from gfa2network_amd import synth
+
+    dtype = np.dtype(dtype)
+    out_t = np.float32 if dtype.itemsize == 1 or dtype == np.float32 else np.float64
+    if count <= DUMP_SAMPLE:
+        runs = [(0, count)]
+    else:
+        offs = np.random.Generator(np.random.PCG64(seed)).integers(0, count - DUMP_RUN, DUMP_SAMPLE // DUMP_RUN - 2)
+        runs = [(int(o), DUMP_RUN) for o in (0, *np.sort(offs), count - DUMP_RUN)]
+    host = np.empty(sum(n for _, n in runs), dtype=dtype)
+    pos = 0
+    for off, n in runs:
+        if n and synth._lib().g2n_synth_download(host[pos:].ctypes.data, ptr + off * dtype.itemsize,
+                                                 n * dtype.itemsize):
+            raise RuntimeError(f"--dump-outputs: reading {name} back failed")
+        pos += n
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), host.astype(out_t))
+
+
+def dump_result(out_dir: str, res) -> None:
+    """--dump-outputs of a g2n_build_device result (device pointers, valid until the context's next
+    build): the CSR, the node names and the counts a caller reads from the result."""
+    import numpy as np
+
+    from gfa2network_amd import _native as nat
+
+    idx = np.int64 if res.index_width == 8 else np.int32
+    n, nnz = int(res.n_nodes), int(res.nnz)
+    dump_array(out_dir, "indptr", res.indptr, n + 1, idx, 1)
+    dump_array(out_dir, "indices", res.indices, nnz, idx, 2)
+    dump_array(out_dir, "data", res.data, nnz, nat.CODE_DTYPES[res.dtype], 3)
+    if res.names_offsets:
+        dump_array(out_dir, "names_offsets", res.names_offsets, n + 1, np.int64, 4)
+        dump_array(out_dir, "names_blob", res.names_blob, int(res.names_bytes), np.uint8, 5)
+    np.save(os.path.join(out_dir, "counts.npy"),
+            np.array([res.n_lines, res.n_records, res.n_edges, n, nnz, res.names_bytes, res.index_width],
+                     dtype=np.float64))
 
 
 def config_leg(lib, nat, synth, wl, device: int, steps: int, warmup: int) -> dict:
@@ -582,7 +651,7 @@ def main_sharded(args, wl):
     import torch.distributed as dist
 
     world, rank, local = _dist_setup(args.gpus, always=True)
-    leg = sharded_leg(args, wl, world, rank, local, args.names, args.force_protocol)
+    leg = sharded_leg(args, wl, world, rank, local, args.names, args.force_protocol, one_gpu=args.full)
     alt = None
     if not args.no_alt and args.names == "decimal":
         try:
@@ -646,6 +715,9 @@ def main():
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.workload is None:
         args.workload = "C5" if max(world_env, args.gpus) > 1 else "C4"
+    if args.dump_outputs and (args.workload == "C5" or args.shard or args.e2e_only):
+        raise SystemExit("bench.py: --dump-outputs writes the result of the one-GPU device-resident build "
+                         "(g2n_build_device); sharded and --e2e-only runs return none")
     if (args.workload == "C5" or args.shard) and not args.e2e_only:
         from gfa2network_amd import synth
 
@@ -698,6 +770,8 @@ def main():
     _barrier(world)
     elapsed = time.perf_counter() - t0
     elapsed = _max_over_ranks(world, elapsed)
+    if args.dump_outputs and rank == 0:  # what the last timed step left in the context
+        dump_result(args.dump_outputs, res)
 
     n_edges, n_nodes, nnz, in_bytes = int(res.n_edges), int(res.n_nodes), int(res.nnz), int(res.input_bytes)
     # the same build through the hash dictionary (what inputs without decimal segment ids take)

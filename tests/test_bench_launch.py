@@ -83,6 +83,25 @@ def test_dist_setup_without_a_group_refuses_more_gpus(monkeypatch):
     assert bench._dist_setup(1) == (1, 0, 0)
 
 
+def test_only_full_runs_the_legs_beyond_the_timed_steps(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench._args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 1, False, None)
+    assert a.no_alt and a.no_e2e and a.no_cpu_baseline and a.no_c5_reference
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-e2e", "--dump-outputs", "d"])
+    a = bench._args()
+    assert a.full and a.no_e2e and a.dump_outputs == "d"
+    assert not (a.no_alt or a.no_cpu_baseline or a.no_c5_reference)
+
+
+@pytest.mark.parametrize("extra", (["--workload", "C5"], ["--shard"], ["--e2e-only"]))
+def test_dump_outputs_is_refused_where_no_device_result_exists(monkeypatch, extra):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--dump-outputs", "d"] + extra)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    with pytest.raises(SystemExit, match="--dump-outputs"):  # before anything touches a GPU
+        bench.main()
+
+
 def test_build_traffic_sums_every_build_kernel_once_per_launch():
     """The C2 / C3 legs' whole-build HBM traffic (bench.build_traffic): every kernel's per-launch
     2 x FETCH_SIZE + WRITE_SIZE times its launches, the input generator's kernels left out — from the
