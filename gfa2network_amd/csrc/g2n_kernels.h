@@ -19,14 +19,8 @@
 namespace g2n {
 
 constexpr int kTPB = 256;
-#ifndef G2N_TILE_BYTES  // experiment builds (tools/exp_build.sh) may override the tile shape
-#define G2N_TILE_BYTES 32768
-#endif
-#ifndef G2N_TILE_HALO
-#define G2N_TILE_HALO 2048
-#endif
-constexpr uint64_t kTile = G2N_TILE_BYTES;    // input bytes per front-end block (K1, K2)
-constexpr uint32_t kTileHalo = G2N_TILE_HALO; // bytes staged past the tile for lines that end beyond it
+constexpr uint64_t kTile = 32768;     // input bytes per front-end block (K1, K2)
+constexpr uint32_t kTileHalo = 2048;  // bytes staged past the tile for lines that end beyond it
 
 enum : uint8_t { kSkip = 0, kUnknown = 1, kS = 2, kEdge = 3, kPO = 4 };
 
@@ -111,9 +105,6 @@ struct ParseOpts {
   // on its group's count (the group's order of tiles is arbitrary: only for consumers that do not
   // need stream order — the unweighted bucket partition); rows / cols already point at the base
   uint32_t grouped;
-  // experiment (G2N_K2_PREFETCH): the one-tile-per-block lean parse warms the cache with tile
-  // blockIdx + pf_dist (0: off)
-  uint32_t pf_dist;
   // the extended tile-local lean parse (k_tile_lean kExt: bidirected keys, one integer weight tag):
   // edge e's weight at ew[e] (the tile slots' layout, one double per edge line); the weight tag's
   // bytes little-endian (wt_len <= 8) for the comparison against the staged line
@@ -174,7 +165,7 @@ struct EdgeIn {
 };
 
 // ---- kernels (g2n_kernels.hip) ----
-// K1-K2 (tile front end: k_tile_count, k_tile_parse, k_parse_deferred, k_weights_slow,
+// K1-K2 (tile front end: k_tile_count_r, k_tile_parse, k_parse_deferred, k_weights_slow,
 // k_error_detail, k_count_records) are defined in g2n_kernels.hip (same translation unit).
 template <int kMode>
 __global__ void k_insert_round(const uint8_t* in, uint64_t in_len, TouchIn T, uint64_t n_t, DictEntry* table,

@@ -207,29 +207,13 @@ constexpr uint32_t kChunkIters = kTileChunks / kTPB;       // chunks per thread
 // t + 256 j; all loads are issued before the first LDS write.  (A persistent variant that loads
 // tile i + G while parsing tile i measured slower on gfx950: the prefetch registers took K2 from
 // 80 to 212 VGPRs, 2 waves/SIMD, 6.3 -> 10.7 ms on C4.)
-#ifndef G2N_LEAN_LINK  // experiment builds: 0 = the edge line's five tabs by five ctz (round 5)
-#define G2N_LEAN_LINK 1
-#endif
-#ifndef G2N_EDGE_ONLY  // experiment builds: 0 = no edge-only parse loop in k_tile_lean (round 5)
-#define G2N_EDGE_ONLY 1
-#endif
-#ifndef G2N_MASK2  // experiment builds: 0 = the lean tile's two bitmaps by two mask16 (round 5)
-#define G2N_MASK2 1
-#endif
-#ifndef G2N_EDGE_FLAT  // experiment builds: 0 = the edge-only loop through lean_line (branch per check)
-#define G2N_EDGE_FLAT 1
-#endif
-#ifndef G2N_LOAD_UNIFORM  // experiment builds: 0 = per-chunk bounds on every tile load (round 5)
-#define G2N_LOAD_UNIFORM 1
-#endif
-
 template <uint32_t kHalo, uint32_t kT = kTPB>
 struct TileRegs {
   static constexpr uint32_t kChunks = (uint32_t)((kTile + kHalo) / 16);
   static constexpr uint32_t kPer = (kChunks + kT - 1) / kT;
   uint4 r[kPer];
   __device__ inline void load(const uint8_t* __restrict__ in, uint64_t len, uint64_t t0) {
-    if (G2N_LOAD_UNIFORM && t0 + (uint64_t)kChunks * 16 <= len) {  // (block-uniform) every chunk is input
+    if (t0 + (uint64_t)kChunks * 16 <= len) {  // (block-uniform) every chunk is input
 #pragma unroll
       for (uint32_t j = 0; j < kPer; j++) {
         const uint32_t c = j * kT + threadIdx.x;
@@ -332,95 +316,11 @@ __device__ __host__ inline TileCnt operator+(const TileCnt& a, const TileCnt& b)
                  a.recs + b.recs};
 }
 
-template <class T>
-__device__ inline T block_sum(T v, T* lds /* >= kTPB / 64 */) {
-  v = wave_reduce_sum(v);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = 0;
-#pragma unroll
-  for (int w = 0; w < kTPB / 64; w++) t += lds[w];
-  __syncthreads();
-  return t;
-}
-
-// exclusive scan over the block (thread order) of one u64 per thread; *tot = block total
-__device__ inline unsigned long long block_excl_scan_u64(unsigned long long v, unsigned long long* tot,
-                                                         unsigned long long* lds /* >= kTPB / 64 */) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  unsigned long long x = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    unsigned long long y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) lds[wid] = x;
-  __syncthreads();
-  unsigned long long wbase = 0, t = 0;
-#pragma unroll
-  for (int q = 0; q < kTPB / 64; q++) {
-    const unsigned long long y = lds[q];
-    if (q < wid) wbase += y;
-    t += y;
-  }
-  __syncthreads();
-  *tot = t;
-  return wbase + x - v;
-}
-
-// pass 1: per tile, the '\n', lines, touches, edges, S lines and records it holds.  Per-tile
-// counts are < 2^16 (32 KiB tiles), so four of them share one block reduction.
-__global__ void __launch_bounds__(kTPB) k_tile_count(const uint8_t* __restrict__ in, uint64_t len, uint32_t tps,
-                                                     uint32_t tpe, TileCnt* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint8_t buf[kTile + 16];
-  __shared__ unsigned long long red[kTPB / 64];
-  const uint64_t t0 = (uint64_t)blockIdx.x * kTile;
-  {
-    TileRegs<16> R;
-    R.load(in, len, t0);
-    R.store(buf);
-  }
-  const bool tile_prev_nl = t0 == 0 || in[t0 - 1] == '\n';
-  __syncthreads();
-  uint32_t nl = 0, lines = 0, edges = 0, segs = 0, po = 0;
-#pragma unroll 2
-  for (uint32_t j = 0; j < kChunkIters; j++) {
-    const uint32_t c = j * kTPB + threadIdx.x;
-    uint32_t m, st;
-    chunk_masks(buf, c, t0, len, tile_prev_nl, m, st, *(const uint4*)(buf + 16 * c));
-    nl += __popc(m);
-    lines += __popc(st);
-    while (st) {
-      const uint32_t o = 16 * c + __builtin_ctz(st);
-      st &= st - 1;
-      const uint8_t k = kind_at(buf, o, t0 + o, len);
-      segs += k == kS;
-      edges += k == kEdge;
-      po += k == kPO;
-    }
-  }
-  const unsigned long long a = block_sum((unsigned long long)nl | ((unsigned long long)lines << 16) |
-                                             ((unsigned long long)segs << 32) | ((unsigned long long)edges << 48),
-                                         red);
-  const unsigned long long b = block_sum((unsigned long long)po, red);
-  if (threadIdx.x == 0) {
-    TileCnt cnt;
-    cnt.nl = a & 0xFFFF;
-    cnt.lines = (a >> 16) & 0xFFFF;
-    cnt.segs = (a >> 32) & 0xFFFF;
-    cnt.edges = a >> 48;
-    cnt.touches = cnt.segs * tps + cnt.edges * tpe;
-    cnt.recs = cnt.segs + cnt.edges + b;
-    out[blockIdx.x] = cnt;
-  }
-}
-
-// K1 without LDS (G2N_K1_REG): thread t of a tile's 512 holds the 16-byte chunks t + 512 j in
-// registers (coalesced loads), the byte before / after a chunk from lane t - 1 / t + 1 (one global
-// byte read per wave and chunk row at each end), each line start's first two bytes picked from the
-// registers.  k_tile_count stages the tile in LDS and reads the starts' bytes back from it.
-#ifndef G2N_K1_REG
-#define G2N_K1_REG 1
-#endif
+// pass 1 (K1): per tile, the '\n', lines, touches, edges, S lines and records it holds.  Per-tile counts
+// are < 2^16 (32 KiB tiles), so four of them share one reduction.  No LDS staging: thread t of a tile's
+// 512 holds the 16-byte chunks t + 512 j in registers (coalesced loads), the byte before / after a chunk
+// from lane t - 1 / t + 1 (one global byte read per wave and chunk row at each end), each line start's
+// first two bytes picked from the registers.
 constexpr uint32_t kK1TPB = 512;
 constexpr uint32_t kK1Per = (uint32_t)(kTile / 16) / kK1TPB;
 __device__ inline uint32_t chunk_byte(uint4 c, uint32_t b) {  // byte b (< 16) of a chunk
@@ -1044,45 +944,14 @@ __device__ inline bool dec_name(const uint8_t* buf, uint32_t x, uint32_t l, cons
   return dec_lds(buf, x, l, v);
 }
 
-// dec_lds's 1-8 digit case on words already loaded: w0 / w1 = the aligned 8-byte LDS words at
-// (x & ~7) and (x & ~7) + 8.  false for anything else (the caller takes dec_lds for 9-10 digits).
-__device__ inline bool dec_words(uint64_t w0, uint64_t w1, uint32_t x, uint32_t l, uint64_t* v) {
-  if (l == 0 || l > 8) return false;
-  const uint32_t sh = (x & 7u) * 8;
-  uint64_t w = w0 >> sh;
-  if (sh && (x & 7u) + l > 8) w |= w1 << (64 - sh);
-  const uint64_t keep = l == 8 ? ~0ull : ((1ull << (8 * l)) - 1);
-  w &= keep;
-  const uint64_t zeros = 0x3030303030303030ull & keep;
-  if ((w & 0xF0F0F0F0F0F0F0F0ull & keep) != zeros ||
-      (((w & 0x0F0F0F0F0F0F0F0Full) + 0x0606060606060606ull) & 0xF0F0F0F0F0F0F0F0ull & keep) != 0 ||
-      (w & 0xFF) == '0')
-    return false;
-  const uint64_t d = (w - zeros) << (8 * (8 - l));
-  auto four = [](uint32_t y) {
-    y = ((y << 3) + (y << 1) + (y >> 8)) & 0x00FF00FFu;
-    return ((y << 6) + (y << 5) + (y << 2) + (y >> 16)) & 0xFFFFu;
-  };
-  *v = (uint64_t)(four((uint32_t)d) * 10000u + four((uint32_t)(d >> 32)));
-  return true;
-}
-
-// tab bits of the 64 staged bytes from chunk q: from the tile's tab bitmap, or (tabm == nullptr)
-// recomputed from the staged bytes (the LDS-lean instance keeps no bitmap)
-#ifndef G2N_TAB_B64  // 1: the window from two aligned 8-byte LDS reads (C4 parse 3.47 -> 3.43 ms); 0: four u16 reads
-#define G2N_TAB_B64 1
-#endif
+// tab bits of the 64 staged bytes from chunk q: from the tile's tab bitmap (two aligned 8-byte LDS
+// reads), or (tabm == nullptr) recomputed from the staged bytes
 __device__ inline uint64_t tab_window(const uint8_t* buf, const uint16_t* tabm, uint32_t q) {
-#if G2N_TAB_B64
   if (tabm) {  // tabm is 16-byte aligned with 8 entries of padding past its last window
     const uint32_t a = q & ~3u, sh = (q & 3u) * 16;
     const uint64_t lo = *(const uint64_t*)(tabm + a), hi = *(const uint64_t*)(tabm + a + 4);
     return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
   }
-#endif
-  if (tabm)
-    return (uint64_t)tabm[q] | ((uint64_t)tabm[q + 1] << 16) | ((uint64_t)tabm[q + 2] << 32) |
-           ((uint64_t)tabm[q + 3] << 48);
   uint64_t w = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) w |= (uint64_t)mask16(*(const uint4*)(buf + 16 * (q + i)), 0x09090909u) << (16 * i);
@@ -1243,7 +1112,7 @@ __device__ inline bool lean_line(const uint8_t* buf, const uint16_t* tabm, uint3
     return true;
   }
   if (k != kEdge) return false;
-  if constexpr (!kExt && G2N_LEAN_LINK) {  // the plain decimal build: two tab searches (lean_link)
+  if constexpr (!kExt) {  // the plain decimal build: two tab searches (lean_link)
     uint32_t la, lb;
     if (!lean_link(buf, m, so, la, lb)) return false;
     if (op.tile_pad && eb >= op.tile_pad) is.fail = 1;  // the tile's slot is full: give up
@@ -1343,44 +1212,25 @@ struct DeferredLine {  // at most one per tile: the line holding the tile window
 // decoupled look-back over the tiles instead (no K1) measured 12.0 ms on C4 against 2.2 + 6.3
 // ms: in-order waiting across the 8 XCDs (status words polled past the non-coherent L2s) stalls
 // every tile behind the slowest.
-// The tile-local lean instance parses every line through the lean shapes (a line outside them
-// gives that parse up: the full parse runs instead), so it carries none of the general parser's
-// registers (166 -> 116 VGPRs; parse 5.64 -> 5.45 ms on C4).  0: the general parser inline.
-#ifndef G2N_LEAN_ONLY
-#define G2N_LEAN_ONLY 1
-#endif
-#ifndef G2N_LEAN_LDS  // experiment: the LDS-lean tile-local instance (4 blocks per CU)
-#define G2N_LEAN_LDS 0
-#endif
 constexpr uint32_t kTileLines = kTileChunks;            // line starts per window (= chunks: pre[] holds both)
 constexpr uint32_t kLinesPer = kTileLines / kTPB;       // lines classified per thread
 static_assert(kChunkIters % 4 == 0 && kTile <= 32768, "tile layout: per-tile counts fit 16 bits");
 
-// Diagnostics build only (-DG2N_K2_STAMPS, tools/k2_stamps.py): per tile, the wall clock at the
-// block's phase boundaries (thread 0) and the hardware id of the CU it ran on.
+// Diagnostics build only (-DG2N_K2_STAMPS, tools/k2_stamps.py): per tile of k_tile_lean, the wall clock
+// at the block's phase boundaries (thread 0) and the hardware id of the CU it ran on.
 #ifdef G2N_K2_STAMPS
 constexpr int kK2Stamps = 10;
 __device__ unsigned long long* g2n_k2_stamps;
-#define K2_STAMP(k)                                                                               \
-  do {                                                                                            \
-    if (kLocal && threadIdx.x == 0) g2n_k2_stamps[blockIdx.x * kK2Stamps + (k)] = wall_clock64(); \
-  } while (0)
 #define K2_LEAN_STAMP(k)                                                                 \
   do {                                                                                   \
     if (threadIdx.x == 0) g2n_k2_stamps[tile * kK2Stamps + (k)] = wall_clock64();        \
   } while (0)
 #else
-#define K2_STAMP(k) \
-  do {              \
-  } while (0)
 #define K2_LEAN_STAMP(k) \
   do {                   \
   } while (0)
 #endif
 
-// kLocal: the tile-local lean parse (ParseOpts.tile_pad; lean, not bidirected, no weight tag, no
-// strip — fixed at compile time, so that instance carries none of the other paths' code)
-template <bool kLocal>
 __global__ void __launch_bounds__(kTPB) k_tile_parse(const uint8_t* __restrict__ in, uint64_t len,
                                                      const TileCnt* __restrict__ base, uint32_t tps, uint32_t tpe,
                                                      ParseOpts op, uint64_t* __restrict__ ls,
@@ -1388,90 +1238,56 @@ __global__ void __launch_bounds__(kTPB) k_tile_parse(const uint8_t* __restrict__
                                                      uint64_t* __restrict__ worklist,
                                                      DeferredLine* __restrict__ deferred, uint64_t n_tiles,
                                                      TileCnt* __restrict__ tcnt_out, TileLean* __restrict__ tlean) {
-  // kDiet (the LDS-lean tile-local instance): half-size line windows, u16 chunk ranks aliased with
-  // the u32 line prefixes, no kind array and no tab bitmap (both re-read from the staged bytes)
-  constexpr bool kDiet = kLocal && G2N_LEAN_LDS;
-  constexpr uint32_t kWinL = kDiet ? kTileLines / 2 : kTileLines;
-  constexpr uint32_t kLinesPerW = kWinL / kTPB;
   __shared__ __attribute__((aligned(16))) uint8_t buf[kTile + kTileHalo + 16];
-  __shared__ __attribute__((aligned(16))) uint16_t starts[kWinL];
-  __shared__ __attribute__((aligned(16))) uint32_t pre[kDiet ? kTileChunks / 2 : kTileChunks];  // chunk ranks, then line prefixes
-  uint16_t* const pre16 = (uint16_t*)pre;
-  __shared__ uint8_t lkind[kDiet ? 1 : kTileLines];
+  __shared__ __attribute__((aligned(16))) uint16_t starts[kTileLines];
+  __shared__ __attribute__((aligned(16))) uint32_t pre[kTileChunks];  // chunk ranks, then line prefixes
+  __shared__ uint8_t lkind[kTileLines];
   __shared__ uint32_t red[kTPB / 64];
   constexpr uint32_t kMaskChunks = (uint32_t)((kTile + kTileHalo) / 16) + 4;  // + 4: tab_bits reads 4 ahead
-  __shared__ __attribute__((aligned(16))) uint16_t tabm_s[kDiet ? 1 : kMaskChunks];
-  uint16_t* const tabm = kDiet ? nullptr : tabm_s;
+  __shared__ __attribute__((aligned(16))) uint16_t tabm_s[kMaskChunks];
+  uint16_t* const tabm = tabm_s;
   const uint64_t tile = blockIdx.x;
   const uint64_t t0 = tile * kTile;
-  K2_STAMP(0);
   {
     TileRegs<kTileHalo> R;
     R.load(in, len, t0);
     R.store(buf);
   }
   const bool tile_prev_nl = t0 == 0 || in[t0 - 1] == '\n';
-  constexpr bool local = kLocal;  // tile-local lean parse: no bases (no K1); counts come out
-  if constexpr (kLocal) {
-    op.bidir = op.keep = op.strip = op.has_wt = 0;
-    tps = 1;
-    tpe = 2;
-    __builtin_assume(op.rows != nullptr && op.tile_pad != 0);
-  } else {
-    op.tile_pad = 0;
-  }
-  const TileCnt b = local ? TileCnt{} : base[tile];
+  op.tile_pad = 0;
+  const TileCnt b = base[tile];
   __syncthreads();
-  K2_STAMP(1);
   // the tile's tab bitmap (bytes past len: 0): the tile's own chunks come with pass (1), here the halo's
-  if constexpr (!kDiet)
-    for (uint32_t c = kTileChunks + threadIdx.x; c < kMaskChunks; c += kTPB)
-      tabm[c] = (uint16_t)(16 * c + 16 <= kTile + kTileHalo + 16 ? mask16(*(const uint4*)(buf + 16 * c), 0x09090909u) : 0u);
+  for (uint32_t c = kTileChunks + threadIdx.x; c < kMaskChunks; c += kTPB)
+    tabm[c] = (uint16_t)(16 * c + 16 <= kTile + kTileHalo + 16 ? mask16(*(const uint4*)(buf + 16 * c), 0x09090909u) : 0u);
   const uint64_t w1 = t0 + kTile + kTileHalo < len ? t0 + kTile + kTileHalo : len;
   Src L{buf, t0, t0 + kTile + kTileHalo + 16};  // bytes past len are staged as 0
   L.tm = tabm;
   L.tm_lim = t0 + kTile + kTileHalo;
   // (1) start masks of this thread's chunks (kept), counts -> ranks
   uint32_t stm[kChunkIters / 2];
-  uint32_t n_nl = 0;
 #pragma unroll
   for (uint32_t j = 0; j < kChunkIters; j++) {
     const uint32_t c = j * kTPB + threadIdx.x;
     const uint4 v = *(const uint4*)(buf + 16 * c);
-    if constexpr (!kDiet) tabm[c] = (uint16_t)mask16(v, 0x09090909u);
+    tabm[c] = (uint16_t)mask16(v, 0x09090909u);
     uint32_t m, st;
     chunk_masks(buf, c, t0, len, tile_prev_nl, m, st, v);
     if (j & 1) stm[j >> 1] |= st << 16;
     else stm[j >> 1] = st;
-    if constexpr (kDiet) pre16[c] = (uint16_t)__popc(st);
-    else pre[c] = (uint32_t)__popc(st);
-    if constexpr (kLocal) n_nl += (uint32_t)__popc(m);
+    pre[c] = (uint32_t)__popc(st);
   }
   __syncthreads();
-  K2_STAMP(2);
   uint32_t n_starts;
   {  // kChunkIters consecutive chunk counts per thread (4-word vector accesses)
     uint32_t q[kChunkIters];
-    if constexpr (kDiet) {  // 8 u16 counts per 16-byte access
 #pragma unroll
-      for (uint32_t k = 0; k < kChunkIters; k += 8) {
-        const uint4 v = *(const uint4*)(pre16 + kChunkIters * threadIdx.x + k);
-        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          q[k + 2 * i] = x[i] & 0xFFFFu;
-          q[k + 2 * i + 1] = x[i] >> 16;
-        }
-      }
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < kChunkIters; k += 4) {
-        const uint4 v = *(const uint4*)(pre + kChunkIters * threadIdx.x + k);
-        q[k] = v.x;
-        q[k + 1] = v.y;
-        q[k + 2] = v.z;
-        q[k + 3] = v.w;
-      }
+    for (uint32_t k = 0; k < kChunkIters; k += 4) {
+      const uint4 v = *(const uint4*)(pre + kChunkIters * threadIdx.x + k);
+      q[k] = v.x;
+      q[k + 1] = v.y;
+      q[k + 2] = v.z;
+      q[k + 3] = v.w;
     }
     uint32_t sum = 0;
 #pragma unroll
@@ -1484,31 +1300,21 @@ __global__ void __launch_bounds__(kTPB) k_tile_parse(const uint8_t* __restrict__
       q[k] = ex;
       ex += t;
     }
-    if constexpr (kDiet) {  // ranks < 2^15 (a chunk past the last start may wrap: never read)
 #pragma unroll
-      for (uint32_t k = 0; k < kChunkIters; k += 8)
-        *(uint4*)(pre16 + kChunkIters * threadIdx.x + k) =
-            make_uint4((q[k] & 0xFFFFu) | (q[k + 1] << 16), (q[k + 2] & 0xFFFFu) | (q[k + 3] << 16),
-                       (q[k + 4] & 0xFFFFu) | (q[k + 5] << 16), (q[k + 6] & 0xFFFFu) | (q[k + 7] << 16));
-    } else {
-#pragma unroll
-      for (uint32_t k = 0; k < kChunkIters; k += 4)
-        *(uint4*)(pre + kChunkIters * threadIdx.x + k) = make_uint4(q[k], q[k + 1], q[k + 2], q[k + 3]);
-    }
+    for (uint32_t k = 0; k < kChunkIters; k += 4)
+      *(uint4*)(pre + kChunkIters * threadIdx.x + k) = make_uint4(q[k], q[k + 1], q[k + 2], q[k + 3]);
   }
   const uint64_t idx0 = b.nl + (tile_prev_nl ? 0 : 1);  // index of the tile's first line
   __syncthreads();
-  K2_STAMP(3);
   uint32_t rank[kChunkIters];
 #pragma unroll
-  for (uint32_t j = 0; j < kChunkIters; j++) rank[j] = kDiet ? (uint32_t)pre16[j * kTPB + threadIdx.x] : pre[j * kTPB + threadIdx.x];
-  uint64_t t_run = b.touches, e_run = b.edges, s_run = 0;
-  uint32_t n_po = 0;
+  for (uint32_t j = 0; j < kChunkIters; j++) rank[j] = pre[j * kTPB + threadIdx.x];
+  uint64_t t_run = b.touches, e_run = b.edges;
   unsigned long long unk = ~0ull;
   IntState is;
   const bool lean_fast = op.rows && !op.bidir && !op.has_wt && !op.strip;
-  for (uint32_t w0 = 0; w0 < n_starts; w0 += kWinL) {
-    const uint32_t n_win = n_starts - w0 < kWinL ? n_starts - w0 : kWinL;
+  for (uint32_t w0 = 0; w0 < n_starts; w0 += kTileLines) {
+    const uint32_t n_win = n_starts - w0 < kTileLines ? n_starts - w0 : kTileLines;
     __syncthreads();  // `pre` (ranks, or the last window's prefixes) is no longer read
     // (3) the window's starts, in order
 #pragma unroll
@@ -1519,77 +1325,37 @@ __global__ void __launch_bounds__(kTPB) k_tile_parse(const uint8_t* __restrict__
       while (st) {
         const uint32_t o = 16 * c + __builtin_ctz(st);
         st &= st - 1;
-        if (r >= w0 && r < w0 + kWinL) starts[r - w0] = (uint16_t)o;
+        if (r >= w0 && r < w0 + kTileLines) starts[r - w0] = (uint16_t)o;
         r++;
       }
     }
     __syncthreads();
-    if (w0 == 0) K2_STAMP(4);
     // kinds of kLinesPer consecutive lines per thread; prefix counts of S and edge lines
     uint32_t cs = 0, ce = 0;
-    uint8_t kk[kLinesPerW];
+    uint8_t kk[kLinesPer];
 #pragma unroll
-    for (uint32_t q = 0; q < kLinesPerW; q++) {
-      const uint32_t j = kLinesPerW * threadIdx.x + q;
+    for (uint32_t q = 0; q < kLinesPer; q++) {
+      const uint32_t j = kLinesPer * threadIdx.x + q;
       uint8_t k = kSkip;
       if (j < n_win) {
         const uint32_t o = starts[j];
         k = kind_at(buf, o, t0 + o, len);
-        if constexpr (!kDiet) lkind[j] = k;
+        lkind[j] = k;
       }
       kk[q] = k;
       cs += k == kS;
       ce += k == kEdge;
-      if constexpr (kLocal) n_po += k == kPO;
     }
     uint32_t ex;
     const uint32_t tot = block_excl_scan_u32((cs << 16) | ce, &ex, red);
 #pragma unroll
-    for (uint32_t q = 0; q < kLinesPerW; q++) {
-      const uint32_t j = kLinesPerW * threadIdx.x + q;
+    for (uint32_t q = 0; q < kLinesPer; q++) {
+      const uint32_t j = kLinesPer * threadIdx.x + q;
       if (j < n_win) pre[j] = ex;
       ex += ((uint32_t)(kk[q] == kS) << 16) | (uint32_t)(kk[q] == kEdge);
     }
     __syncthreads();
-    if (w0 == 0) K2_STAMP(5);
     // (4) parse: lane-parallel lines
-#if G2N_LEAN_ONLY
-    if constexpr (kLocal) {  // the lean shapes only: any other line gives the tile-local parse up
-#pragma unroll 1
-      for (uint32_t j = threadIdx.x; j < n_win; j += kTPB) {
-        const uint32_t o = starts[j];
-        const uint8_t k = kDiet ? kind_at(buf, o, t0 + o, len) : lkind[j];
-        if (k == kUnknown) {
-          const uint64_t i = idx0 + w0 + j;
-          unk = i < unk ? i : unk;
-        }
-        if (k != kS && k != kEdge && k != kPO) continue;
-        uint32_t next = 0;  // 1 + the line's '\n' (or its virtual one at EOF), tile-local
-        if (j + 1 < n_win) {
-          next = starts[j + 1];
-        } else {
-          const uint32_t lim = (uint32_t)(len - t0 < kTile + kTileHalo ? len - t0 : kTile + kTileHalo);
-          uint32_t x = o;
-          while (x < lim && buf[x] != '\n') x++;
-          if (x < lim || lim == len - t0) next = x + 1;
-        }
-        if (!next) {
-          is.fail = 1;
-          continue;
-        }
-        if (k == kPO) {  // parser.py:229-247, 343-361: >= 3 fields, nothing else for the matrix
-          const uint32_t n = next - 1 - o, sh = o & 15;
-          const uint64_t w = tab_window(buf, tabm, o >> 4);
-          if (__popcll((w >> sh) & ((1ull << (n > 48 ? 48 : n)) - 1)) < 2) is.fail = 1;  // the full parse decides
-          continue;
-        }
-        const uint32_t pr = pre[j];
-        const uint64_t tb = t_run + (uint64_t)(pr >> 16) + 2 * (uint64_t)(pr & 0xFFFF);
-        const uint64_t eb = e_run + (pr & 0xFFFF);
-        if (!lean_line(buf, tabm, o, next, k, t0, tb, eb, op, T, is)) is.fail = 1;
-      }
-    } else
-#endif
 #pragma unroll 1
     for (uint32_t j = threadIdx.x; j < n_win; j += kTPB) {
       const uint32_t o = starts[j];
@@ -1610,71 +1376,17 @@ __global__ void __launch_bounds__(kTPB) k_tile_parse(const uint8_t* __restrict__
         if (lean_fast && known && lean_line(buf, tabm, o, starts[j + 1], k, t0, tb, eb, op, T, is)) continue;
         const uint64_t bound = known ? t0 + starts[j + 1] : w1;
         if (!parse_line(L, len, bound, known, i, k, p, tb, eb, op, T, E, ctl, worklist, is)) {
-          if (local) {  // no global positions for a deferred line: the tile-local parse gives up
-            is.fail = 1;
-          } else {
-            const unsigned long long d = atomicAdd(&ctl->n_deferred, 1ull);
-            if (d < n_tiles) deferred[d] = DeferredLine{i, p, (uint32_t)tb, (uint32_t)eb, k, 0};
-          }
+          const unsigned long long d = atomicAdd(&ctl->n_deferred, 1ull);
+          if (d < n_tiles) deferred[d] = DeferredLine{i, p, (uint32_t)tb, (uint32_t)eb, k, 0};
         }
       }
     }
     t_run += (uint64_t)(tot >> 16) * tps + (uint64_t)(tot & 0xFFFF) * tpe;
     e_run += tot & 0xFFFF;
-    s_run += tot >> 16;
   }
-#ifdef G2N_K2_STAMPS
-  K2_STAMP(6);  // thread 0's own lines parsed
-  __syncthreads();
-  K2_STAMP(7);  // every line of the block parsed
-#endif
   unk = wave_reduce_min(unk);
   if ((threadIdx.x & 63) == 0 && unk != ~0ull) atomicMin(&ctl->warn_line, unk);
-  if constexpr (kLocal) {  // the tile's counts (K1's) and its premise evidence
-    if (e_run > op.tile_pad) is.fail = 1;  // more edges than the tile's slot holds
-    uint32_t vm = is.vmax;
-    int32_t dmn = is.dref == kNoS ? 0x7FFFFFFF : is.dref, dmx = is.dref;  // (kNoS is the int32 minimum)
-    for (int o = 32; o > 0; o >>= 1) {
-      vm = max(vm, (uint32_t)__shfl_xor(vm, o, 64));
-      dmn = min(dmn, (int32_t)__shfl_xor(dmn, o, 64));
-      dmx = max(dmx, (int32_t)__shfl_xor(dmx, o, 64));
-    }
-    __shared__ uint32_t rv[kTPB / 64];
-    __shared__ int32_t rmn[kTPB / 64], rmx[kTPB / 64];
-    if ((threadIdx.x & 63) == 0) {
-      rv[threadIdx.x >> 6] = vm;
-      rmn[threadIdx.x >> 6] = dmn;
-      rmx[threadIdx.x >> 6] = dmx;
-    }
-    const uint32_t nlpo = block_sum(n_nl | (n_po << 16), red);  // per-tile counts < 2^16 (barriers)
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < kTPB / 64; w++) {
-        vm = max(vm, rv[w]);
-        dmn = min(dmn, rmn[w]);
-        dmx = max(dmx, rmx[w]);
-      }
-      TileCnt c;
-      c.nl = nlpo & 0xFFFF;
-      c.lines = n_starts;
-      c.segs = s_run;
-      c.edges = e_run;
-      c.touches = t_run;
-      c.recs = s_run + e_run + (nlpo >> 16);
-      tcnt_out[tile] = c;
-      tlean[tile] = TileLean{dmn, dmx, vm};  // no S line: dmn > dmx (the check skips the tile)
-    }
-  }
   if (__ballot(is.fail) && (threadIdx.x & 63) == 0) ctl->int_fail = 1;
-#ifdef G2N_K2_STAMPS
-  K2_STAMP(8);
-  if (kLocal && threadIdx.x == 0) {
-    uint32_t hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    uint32_t xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g2n_k2_stamps[blockIdx.x * kK2Stamps + 9] = ((unsigned long long)xcc << 32) | hw;
-  }
-#endif
 }
 
 // Tile-local lean parse, afterwards: tile t's S lines must name (S lines before t) + their index
@@ -1965,36 +1677,21 @@ __device__ inline bool tail_eq(const uint8_t* __restrict__ in, const TouchIn& T,
 //      record's offset, the fields come from the tab bitmap (lean_line), the result goes to the
 //      tile's COO slot.
 // 512 threads over the same 52 KB of LDS as 256 would use: 3 blocks and 6 waves per SIMD.
-// Same outputs as k_tile_parse<true> (tile counts, premise evidence, COO slot) with one block
-// scan instead of three.  Anything outside the lean shapes — an unsupported record (its warning
+// Same outputs as round 4's tile-local instance of k_tile_parse (tile counts, premise evidence, COO
+// slot) with one block scan instead of three.  Anything outside the lean shapes — an unsupported record (its warning
 // needs global line indices), a line running past the staged window — fails the tile-local parse
 // and the full parse runs (tile_local_parse).
-#ifndef G2N_LEAN_TPB  // experiment builds: 1024 (32-byte regions)
-#define G2N_LEAN_TPB 512
-#endif
-constexpr uint32_t kLeanTPB = G2N_LEAN_TPB;                             // threads per tile
+constexpr uint32_t kLeanTPB = 512;                                      // threads per tile
 constexpr uint32_t kLeanRegion = (uint32_t)(kTile / 16) / kLeanTPB;     // chunks per thread (4)
 // the lean front end's halo: a lean edge line ends at most 48 bytes + its '\n' past its start, and an S /
 // P / O line whose end is out of view needs only its first 48 bytes (round 6: 64 bytes staged past the
 // tile instead of K1 / k_tile_parse's 2 KiB — 0.2 % of the input re-read and masked, not 6.25 %)
-#ifndef G2N_LEAN_HALO
-#define G2N_LEAN_HALO 64
-#endif
-constexpr uint32_t kLeanHalo = G2N_LEAN_HALO;
+constexpr uint32_t kLeanHalo = 64;
 static_assert(kLeanHalo >= 64 && kLeanHalo % 16 == 0, "an edge line's 49 bytes past its start");
 constexpr uint32_t kLeanChunks = (uint32_t)((kTile + kLeanHalo) / 16);  // staged chunks
 constexpr uint32_t kLeanLines = 2048;                                   // line records per window
-#ifndef G2N_LEAN_PAIR  // experiment builds: the decimal parse two lines per lane per step
-#define G2N_LEAN_PAIR 0
-#endif
-#ifndef G2N_CLASSIFY_FLAT  // experiment builds: 0 = the lean classify's starts through line_kind's branches
-#define G2N_CLASSIFY_FLAT 1
-#endif
-#ifndef G2N_LEAN_BATCH  // experiment builds: starts classified per region with their loads batched
-#define G2N_LEAN_BATCH 4
-#endif
-constexpr uint32_t kLeanBatch = G2N_LEAN_BATCH;                         // starts classified with loads batched
-static_assert(kTile <= 32768 && (kLeanRegion == 4 || kLeanRegion == 2),
+constexpr uint32_t kLeanBatch = 4;                                      // starts classified with loads batched
+static_assert(kTile <= 32768 && kLeanRegion == 4,
               "records hold 15-bit offsets; a region's starts fit one 64-bit mask");
 
 __device__ inline uint32_t lean_code(uint8_t kd) {  // record kind: 0 other, 1 S, 2 edge, 3 P / O
@@ -2013,9 +1710,6 @@ __device__ __forceinline__ uint32_t lean_code_flat(uint32_t c0, bool exact, bool
   return exact ? code : 0u;
 }
 
-#ifndef G2N_DPP_SCAN  // experiment builds: 0 = the lean tile's scan / reductions by ds_bpermute shuffles (round 5)
-#define G2N_DPP_SCAN 1
-#endif
 // Wave-wide inclusive scans / reductions by DPP (gfx9 row_shr within 16-lane rows, then row_bcast:15 /
 // row_bcast:31 across rows): one VALU op per step, no LDS crossbar round trip (__shfl_up / __shfl_xor
 // compile to ds_bpermute).  Lanes a step has no source for take the identity (old operand).
@@ -2106,9 +1800,6 @@ __device__ inline T block_excl_scan_n64(T v, T* tot, T* lds /* >= kN / 64 */) { 
 // v is a repeated name: the pass fails), and an edge name costs one random 4-byte read instead of a
 // 32-byte probe plus a key compare.  Same premise and fallbacks as the hash modes.
 enum : int { kLeanDecimal = 0, kLeanClaim = 1, kLeanEdges = 2, kLeanDirClaim = 3, kLeanDirEdges = 4 };
-#ifndef G2N_HL_LINES  // edge lines per thread per step in kLeanEdges (2, four probes in flight: 105 VGPRs, slower)
-#define G2N_HL_LINES 1
-#endif
 
 struct HashLeanArgs {
   const TileCnt* tbase;  // K1's tile bases (exclusive scan of tcnt)
@@ -2137,10 +1828,6 @@ struct HashLeanArgs {
   uint64_t wt_pack;
   double* ew;
 };
-
-#ifndef G2N_DIRECT_STORE  // kLeanDirClaim: 1 = plain stores + a count of the filled slots, 0 = CAS per S line
-#define G2N_DIRECT_STORE 1
-#endif
 
 // The lean hash / direct passes' tiles, from K1's counts: lists[0] / lists[1] = how many tiles hold
 // S or P / O lines (the claim passes) / edge lines (the edge passes), their indices at lists + 2 /
@@ -2217,13 +1904,6 @@ __global__ void __launch_bounds__(256) k_direct_filled(const uint4* __restrict__
   if (threadIdx.x == 0 && red[0] + red[1] + red[2] + red[3])
     atomicAdd(out, (unsigned long long)(red[0] + red[1] + red[2] + red[3]));
 }
-
-#ifndef G2N_DIRECT_LINES  // kLeanDirEdges: edge lines per thread per step (2 random reads each in flight)
-#define G2N_DIRECT_LINES 4
-#endif
-
-
-
 
 // The first min(l, 16) bytes at tile offset x of the staged tile, little-endian, zero padded
 // (aligned 8-byte LDS reads; never past x + l rounded up to 8)
@@ -2394,18 +2074,13 @@ __device__ inline uint32_t lean_find(const uint8_t* __restrict__ in, const HashL
 }
 
 using LeanRegs = TileRegs<kLeanHalo, kLeanTPB>;
-#ifndef G2N_K2_PREFETCH
-#define G2N_K2_PREFETCH 0
-#endif
 
-// One tile of the lean front end.  R holds the tile's staged bytes on entry (loaded by the caller);
-// after they are in LDS, R is refilled with tile next_tile's bytes (next_tile < n_tiles), which stay
-// in flight through this tile's parse — the persistent decimal kernel's prefetch.
+// One tile of the lean front end.  R holds the tile's staged bytes on entry (loaded by the caller).
 template <int kMode, bool kGrouped, bool kExt = false>
 __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64_t len, ParseOpts op, Ctl* ctl,
                                           TileCnt* __restrict__ tcnt_out, TileLean* __restrict__ tlean,
                                           uint32_t* __restrict__ gcount, uint64_t gcap, const HashLeanArgs& H,
-                                          const uint64_t tile, LeanRegs& R, uint64_t next_tile, uint64_t n_tiles) {
+                                          const uint64_t tile, LeanRegs& R) {
   constexpr uint32_t kW = kLeanTPB / 64;
   __shared__ __attribute__((aligned(16))) uint8_t buf[kTile + kLeanHalo + 16];
   __shared__ __attribute__((aligned(16))) uint16_t tabm[kLeanChunks + 8];
@@ -2435,17 +2110,11 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
   for (uint32_t j = 0; j < R.kPer; j++) {
     const uint32_t c = j * kLeanTPB + threadIdx.x;
     if (c < kLeanChunks) {
-#if G2N_MASK2
       const uint32_t tn = mask16x2(R.r[j]);
       tabm[c] = (uint16_t)tn;
       nlm[c] = (uint16_t)(tn >> 16);
-#else
-      tabm[c] = (uint16_t)mask16(R.r[j], 0x09090909u);
-      nlm[c] = (uint16_t)mask16(R.r[j], 0x0A0A0A0Au);
-#endif
     }
   }
-  if (next_tile < n_tiles) R.load(in, len, next_tile * kTile);  // in flight through this tile's parse
   if (threadIdx.x < 8) {  // tab_window reads up to 4 bitmaps past a chunk
     tabm[kLeanChunks + threadIdx.x] = 0;
     nlm[kLeanChunks + threadIdx.x] = 0;
@@ -2461,16 +2130,10 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
   unsigned long long st;
   uint32_t n_nl;
   {
-    unsigned long long nl;
-    if constexpr (kLeanRegion == 4) {
-      const uint2 v = *(const uint2*)(nlm + c0);
-      nl = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
-    } else {
-      nl = *(const uint32_t*)(nlm + c0);
-    }
+    const uint2 v = *(const uint2*)(nlm + c0);
+    const unsigned long long nl = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
     const unsigned long long prev = c0 ? (unsigned long long)(nlm[c0 - 1] >> 15) : (tile_prev_nl ? 1ull : 0ull);
     st = (nl << 1) | prev;
-    if constexpr (kLeanRegion == 2) st &= 0xFFFFFFFFull;
     const uint64_t r0 = t0 + 16ull * c0;  // a start needs a byte: none at or past len
     if (r0 + 16 * kLeanRegion > len) st &= r0 >= len ? 0ull : ((1ull << (len - r0)) - 1);
     n_nl = (uint32_t)__popcll(nl);
@@ -2506,7 +2169,6 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
       x0[q] = buf[o];
       x1[q] = buf[o + 1];
     }
-#if G2N_CLASSIFY_FLAT
     // (round 6) branch-free: unsupported() as selects — the first unknown start that op.tunk takes, or
     // the failure for one it cannot (a first byte >= 0x80 or no op.tunk)
 #pragma unroll
@@ -2527,20 +2189,6 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
       n_e += code == 2;
       n_po += code == 3;
     }
-#else
-#pragma unroll
-    for (uint32_t q = 0; q < kLeanBatch; q++) {
-      if (off[q] == 0xFFFFu) continue;
-      const bool exact = t0 + off[q] + 1 >= len || x0[q] == '\n' || x1[q] == '\t' || x1[q] == '\n';
-      const uint8_t kd = line_kind((uint8_t)x0[q], exact);
-      if (kd == kUnknown) unsupported(q, off[q], x0[q]);
-      const uint32_t code = lean_code(kd);
-      codes |= code << (2 * q);
-      n_s += code == 1;
-      n_e += code == 2;
-      n_po += code == 3;
-    }
-#endif
 #pragma unroll 1
     for (uint32_t q = kLeanBatch; m; q++) {  // more than kLeanBatch lines start in these 64 bytes
       const uint32_t o = 16 * c0 + (uint32_t)__builtin_ctzll(m);
@@ -2555,12 +2203,7 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
   }
   K2_LEAN_STAMP(2);
   unsigned long long tot;
-#if G2N_DPP_SCAN
   const unsigned long long ex = lean_block_scan<kLeanTPB>(n_st, n_s, n_e, &tot, red64);
-#else
-  const unsigned long long ex = block_excl_scan_n64<kLeanTPB>(
-      (unsigned long long)n_st | ((unsigned long long)n_s << 20) | ((unsigned long long)n_e << 40), &tot, red64);
-#endif
   const uint32_t n_lines = (uint32_t)(tot & 0xFFFFFu), s_tot = (uint32_t)((tot >> 20) & 0xFFFFFu),
                  e_tot = (uint32_t)(tot >> 40);
   if (q_unk != ~0u) atomicMin(&s_unk, (((uint32_t)(ex & 0xFFFFFu) + q_unk) << 15) | o_unk);  // (read at the finish)
@@ -2617,7 +2260,7 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
     if constexpr (kMode == kLeanDirEdges) {
       // kDL lines per thread per step: their 2 kDL random reads all in flight at once (the pass is
       // bound by the random-read rate of the direct array, not by the parse)
-      constexpr uint32_t kDL = G2N_DIRECT_LINES;
+      constexpr uint32_t kDL = 4;
 #pragma unroll 1
       for (uint32_t j0 = threadIdx.x; j0 < n_win; j0 += kDL * kLeanTPB) {
         uint32_t va[kDL], vb[kDL], eo[kDL], ori[kDL];  // values (< 2^28), edge index in the window's tile
@@ -2665,8 +2308,9 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
       continue;  // next window
     }
     if constexpr (kMode == kLeanEdges) {
-      // kHL lines per thread per step: their names' first probes are all in flight at once
-      constexpr int kHL = G2N_HL_LINES;
+      // kHL lines per thread per step: their names' first probes are all in flight at once (2, four probes
+      // in flight: 105 VGPRs, slower)
+      constexpr int kHL = 1;
 #pragma unroll 1
       for (uint32_t j0 = threadIdx.x; j0 < n_win; j0 += kHL * kLeanTPB) {
         bool act[kHL];
@@ -2722,109 +2366,12 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
       }
       continue;  // next window
     }
-#if G2N_LEAN_PAIR
-    // decimal ids: two lines per lane per step, every stage's LDS loads for both lines issued
-    // together (rec -> tab window -> name words), the checks branch-free (lean_line's rules)
-    if constexpr (kMode == kLeanDecimal) {
-#pragma unroll 1
-      for (uint32_t j0 = threadIdx.x; j0 < n_win; j0 += 2 * kLeanTPB) {
-        uint32_t o[2], nx[2], cd[2], pf[2];
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-          const uint32_t j = j0 + (uint32_t)q * kLeanTPB;
-          const uint32_t x = j < n_win ? rec[j] : 0u;
-          cd[q] = (x >> 15) & 3u;
-          o[q] = x & 0x7FFFu;
-          pf[q] = x >> 17;
-          nx[q] = cd[q] ? line_next(j, o[q]) : 0u;
-        }
-        uint64_t w[2];
-#pragma unroll
-        for (int q = 0; q < 2; q++) w[q] = tab_window(buf, tabm, o[q] >> 4);
-        uint32_t xa[2], la[2], xb[2], lb[2], oa[2], ob[2];
-        bool good[2];
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-          const uint32_t n = nx[q] - 1 - o[q];
-          uint64_t m = (w[q] >> (o[q] & 15)) & ((1ull << (n > 48 ? 48 : n)) - 1);
-          const uint32_t pc = (uint32_t)__popcll(m);
-          uint32_t p[6];
-#pragma unroll
-          for (int k = 0; k < 6; k++) {
-            p[k] = m ? (uint32_t)__builtin_ctzll(m) : n;
-            m &= m - 1;
-          }
-          const bool s_ok = pc >= 1 && (pc >= 2 || n <= 48);
-          const bool e_ok = n <= 48 && pc >= 5 && p[2] - p[1] == 2 && p[4] - p[3] == 2;
-          const bool po_ok = pc >= 2;
-          good[q] = cd[q] == 0 || (nx[q] != 0 && (cd[q] == 1 ? s_ok : cd[q] == 2 ? e_ok : po_ok));
-          const bool s = cd[q] == 1 && good[q], e = cd[q] == 2 && good[q];
-          xa[q] = s || e ? o[q] + p[0] + 1 : 0u;
-          la[q] = s || e ? p[1] - p[0] - 1 : 0u;
-          xb[q] = e ? o[q] + p[2] + 1 : 0u;
-          lb[q] = e ? p[3] - p[2] - 1 : 0u;
-          oa[q] = e ? o[q] + p[1] + 1 : 0u;  // the orientation bytes
-          ob[q] = e ? o[q] + p[3] + 1 : 0u;
-        }
-        uint64_t wa0[2], wa1[2], wb0[2], wb1[2];
-        uint32_t c2[2], c4[2];
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-          const uint32_t a = xa[q] & ~7u, b = xb[q] & ~7u;
-          wa0[q] = *(const uint64_t*)(buf + a);
-          wa1[q] = *(const uint64_t*)(buf + a + 8);
-          wb0[q] = *(const uint64_t*)(buf + b);
-          wb1[q] = *(const uint64_t*)(buf + b + 8);
-          c2[q] = buf[oa[q]];
-          c4[q] = buf[ob[q]];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-          if (!good[q]) {
-            is.fail = 1;
-            continue;
-          }
-          if (cd[q] == 1) {  // S line: its S index pf (no edge precedes it in the tile)
-            if (is.fail) continue;
-            uint64_t v;
-            const bool dok = la[q] <= 8 ? dec_words(wa0[q], wa1[q], xa[q], la[q], &v) : dec_lds(buf, xa[q], la[q], &v);
-            if (!dok) is.fail = 1;
-            else is.s_name(op, v, pf[q]);
-          } else if (cd[q] == 2) {
-            if ((c2[q] != '+' && c2[q] != '-') || (c4[q] != '+' && c4[q] != '-') || pf[q] >= op.tile_pad) {
-              is.fail = 1;
-              continue;
-            }
-            if (is.fail) continue;
-            uint64_t a, b;
-            const bool aok = la[q] <= 8 ? dec_words(wa0[q], wa1[q], xa[q], la[q], &a) : dec_lds(buf, xa[q], la[q], &a);
-            const bool bok = lb[q] <= 8 ? dec_words(wb0[q], wb1[q], xb[q], lb[q], &b) : dec_lds(buf, xb[q], lb[q], &b);
-            if (!aok || !bok || a > op.n_seg || b > op.n_seg) {
-              is.fail = 1;
-              continue;
-            }
-            const uint32_t vm = (uint32_t)(a > b ? a : b);
-            is.vmax = vm > is.vmax ? vm : is.vmax;
-            const uint64_t eo = (uint64_t)pf[q] * op.ktrip;
-            op.rows[eo] = (int32_t)(a - 1);
-            op.cols[eo] = (int32_t)(b - 1);
-            if (op.ktrip >= 2) {
-              op.rows[eo + 1] = (int32_t)(b - 1);
-              op.cols[eo + 1] = (int32_t)(a - 1);
-            }
-          }
-        }
-      }
-      continue;  // next window
-    }
-#endif
-    if (G2N_EDGE_ONLY && kMode == kLeanDecimal && !kExt && e_tot == n_lines) {  // (block-uniform) edge lines only: no
+    if (kMode == kLeanDecimal && !kExt && e_tot == n_lines) {  // (block-uniform) edge lines only: no
 #pragma unroll 1                                               // record-kind branches (round 6)
       for (uint32_t j = threadIdx.x; j < n_win; j += kLeanTPB) {
         const uint32_t x = rec[j];
         const uint32_t o = x & 0x7FFFu, eb = x >> 17;
         const uint32_t next = line_next(j, o);
-#if G2N_EDGE_FLAT
         uint64_t a, b;
         if (!lean_edge_flat(buf, tabm, o, next, op, kTile + kLeanHalo - 8u, &a, &b) | (eb >= op.tile_pad) |
             (a > op.n_seg) | (b > op.n_seg)) {
@@ -2841,10 +2388,6 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
           op.rows[eo + 1] = (int32_t)(b - 1);
           op.cols[eo + 1] = (int32_t)(a - 1);
         }
-#else
-        if (!next || !lean_line<false>(buf, tabm, o, next, kEdge, t0, 0ull, eb, op, TouchOut{}, is))
-          is.fail = 1;
-#endif
       }
       continue;  // next window
     }
@@ -2877,18 +2420,11 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
           continue;
         }
         const uint32_t id = (uint32_t)(sbase + pref);
-#if G2N_DIRECT_STORE
         // a plain store: a repeated value leaves fewer filled slots than S lines, which one count of
         // the array after the pass finds (k_direct_filled; a verify pass re-staging the tiles measured
         // slower: 4.13 against 3.70 ms)
         H.direct[v] = id;
         claimed_vmax = (uint32_t)v > claimed_vmax ? (uint32_t)v : claimed_vmax;
-#else
-        if (atomicCAS(H.direct + v, ~0u, id) != ~0u) {  // a repeated S name: the classic tiers decide
-          is.fail = 1;
-          continue;
-        }
-#endif
         H.noff[id] = t0 + x;
         H.nlen[id] = l;
         claimed_bytes += l;
@@ -2975,7 +2511,6 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
   if (e_tot > op.tile_pad) is.fail = 1;  // more edges than the tile's slot holds
   uint32_t vm = is.vmax;
   int32_t dmn = is.dref == kNoS ? 0x7FFFFFFF : is.dref, dmx = is.dref;  // (kNoS is the int32 minimum)
-#if G2N_DPP_SCAN
   // (n_nl <= 2^15 and n_po < 2^15 per tile: one packed 32-bit sum)
   const uint32_t c32 = wave_dpp_reduce(n_nl | (n_po << 16), 0u, dpp_add);
   unsigned long long cnt = (unsigned long long)(c32 & 0xFFFFu) | ((unsigned long long)(c32 >> 16) << 20);
@@ -2984,15 +2519,6 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
     dmn = (int32_t)wave_dpp_reduce((uint32_t)dmn, 0x7FFFFFFFu, dpp_smin);
     dmx = (int32_t)wave_dpp_reduce((uint32_t)dmx, 0x80000000u, dpp_smax);
   }
-#else
-  unsigned long long cnt = (unsigned long long)n_nl | ((unsigned long long)n_po << 20);  // per tile < 2^20 each
-  for (int o = 32; o > 0; o >>= 1) {
-    vm = max(vm, (uint32_t)__shfl_xor(vm, o, 64));
-    dmn = min(dmn, (int32_t)__shfl_xor(dmn, o, 64));
-    dmx = max(dmx, (int32_t)__shfl_xor(dmx, o, 64));
-    cnt += __shfl_xor(cnt, o, 64);
-  }
-#endif
   __shared__ uint32_t rv[kW];
   __shared__ int32_t rmn[kW], rmx[kW];
   __shared__ unsigned long long rc[kW];
@@ -3039,13 +2565,8 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
 }
 
 // One block per tile (the hash modes skip the tiles they have nothing to do in before loading them).
-#if G2N_LEAN_PAIR  // the LDS allows 3 blocks (6 waves per SIMD): keep the VGPRs to 80
-#define G2N_LEAN_ATTR __attribute__((amdgpu_flat_work_group_size(kLeanTPB, kLeanTPB), amdgpu_waves_per_eu(6, 6)))
-#else
-#define G2N_LEAN_ATTR __launch_bounds__(kLeanTPB, kLeanTPB == 1024 ? 2 : 1)
-#endif
 template <int kMode, bool kGrouped, bool kExt = false>
-__global__ void G2N_LEAN_ATTR
+__global__ void __launch_bounds__(kLeanTPB, 1)
     k_tile_lean(const uint8_t* __restrict__ in, uint64_t len, ParseOpts op, Ctl* ctl, TileCnt* __restrict__ tcnt_out,
                 TileLean* __restrict__ tlean, uint32_t* __restrict__ gcount, uint64_t gcap, HashLeanArgs H) {
   const uint64_t tile = kMode != kLeanDecimal && H.tlist ? (uint64_t)H.tlist[blockIdx.x] : (uint64_t)blockIdx.x;
@@ -3064,40 +2585,7 @@ __global__ void G2N_LEAN_ATTR
   }
   LeanRegs R;
   R.load(in, len, tile * kTile);
-#if G2N_K2_PREFETCH
-  // experiment: warm the L2 / Infinity Cache with the tile the block G tiles on will stage (G = the
-  // blocks resident at once, a multiple of the 8 XCDs: the same XCD's L2) — one dword per 128-byte
-  // line, into a sink register kept live (and drained) to the end, so no later value shares it
-  uint32_t sink = 0;
-  const uint64_t pf = (tile + op.pf_dist) * kTile + 128ull * threadIdx.x;
-  const bool do_pf = op.pf_dist && threadIdx.x < (kTile + kLeanHalo) / 128 && pf < len;
-  if (do_pf) asm volatile("global_load_dword %0, %1, off" : "=v"(sink) : "v"(in + pf) : "memory");
-#endif
-  lean_tile<kMode, kGrouped, kExt>(in, len, op, ctl, tcnt_out, tlean, gcount, gcap, H, tile, R, ~0ull, 0);
-#if G2N_K2_PREFETCH
-  asm volatile("s_waitcnt vmcnt(0)" : : "v"(sink) : "memory");
-#endif
-}
-
-// The decimal-id parse persistent: a block walks tiles blockIdx.x, + gridDim.x, ... and loads the
-// next one's bytes into registers while it parses the current one (the staged loads' HBM latency
-// was a quarter of a block's time with one tile per block: stamps).
-#ifndef G2N_K2P_WAVES  // waves per SIMD the persistent parse is compiled for (LDS allows 6: VGPRs <= 80)
-#define G2N_K2P_WAVES 6
-#endif
-template <bool kGrouped>
-__global__ void __attribute__((amdgpu_flat_work_group_size(kLeanTPB, kLeanTPB), amdgpu_waves_per_eu(G2N_K2P_WAVES, G2N_K2P_WAVES)))
-    k_tile_lean_p(const uint8_t* __restrict__ in, uint64_t len, ParseOpts op, Ctl* ctl, TileCnt* __restrict__ tcnt_out,
-                  TileLean* __restrict__ tlean, uint32_t* __restrict__ gcount, uint64_t gcap, uint64_t n_tiles) {
-  LeanRegs R;
-  uint64_t tile = blockIdx.x;
-  if (tile < n_tiles) R.load(in, len, tile * kTile);
-#pragma unroll 1
-  for (; tile < n_tiles; tile += gridDim.x) {
-    if (tile != blockIdx.x) __syncthreads();  // the previous tile's LDS fully read
-    lean_tile<kLeanDecimal, kGrouped>(in, len, op, ctl, tcnt_out, tlean, gcount, gcap, HashLeanArgs{}, tile, R,
-                                      tile + gridDim.x, n_tiles);
-  }
+  lean_tile<kMode, kGrouped, kExt>(in, len, op, ctl, tcnt_out, tlean, gcount, gcap, H, tile, R);
 }
 
 // Open-addressing dictionary, 32-byte entries: hdr = (hash tag << 32 | first touch),

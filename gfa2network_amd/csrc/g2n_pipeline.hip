@@ -18,15 +18,6 @@
 
 #include "g2n_internal.h"
 #include "g2n_kernels.hip"
-#ifndef G2N_NO_GROUP_DEFAULT  // 1: never group slots (experiments)
-#define G2N_NO_GROUP_DEFAULT 0
-#endif
-#ifndef G2N_K2_OLD  // 1: the tile-local parse through k_tile_parse<true> (experiments)
-#define G2N_K2_OLD 0
-#endif
-#ifndef G2N_LOOKUP_BATCH  // touches per thread in the S-first lookup round (experiment builds vary it)
-#define G2N_LOOKUP_BATCH 2
-#endif
 #include "g2n_scan.hip"
 #include "g2n_sort.hip"
 #include "g2n_sym.hip"
@@ -51,28 +42,12 @@ enum Slot {
   S_ROUT1, S_UCNT0, S_UCNT1, S_UOFF, S_MCNT, S_MOFF, S_RSCR, S_RFLAG0, S_RFLAG1, S_RVAL0, S_RVAL1, S_TID,
   S_INV, S_TUNK, S_DEFER, S_FOFF64, S_BTC, S_BTV, S_BTOT, S_EBAD, S_ELEN, S_EPOS, S_ETEXT, S_EFIRST, S_EMETA, S_EL0, S_EL1,
   S_PCNT, S_POFF, S_PGRP, S_BSTART, S_SCANST, S_RBOUND, S_ROWSP, S_COLSP, S_TLEAN, S_ZIN, S_ZMEM, S_ZBAD, S_RSK, S_RSV, S_RSCNT, S_RSOFF,
-  S_GCNT, S_TCN, S_FINLB, S_INDPTR64, S_INDICES64, S_WENC, S_W1, S_W2, S_TVAL, S_PW0, S_PW1, S_BSTARTA, S_DIRECT, S_RTOT, S_SCANST2, S_EWP, S_TLIST, S_TNB, S_WENCP, S_NSLOTS
+  S_GCNT, S_TCN, S_INDPTR64, S_INDICES64, S_WENC, S_W1, S_W2, S_TVAL, S_PW0, S_PW1, S_BSTARTA, S_DIRECT, S_RTOT, S_SCANST2, S_EWP, S_TLIST, S_TNB, S_WENCP, S_NSLOTS
 };
 
-#ifndef G2N_MIN_GROUPS  // group slots: fewer tiles per slot until the input has about this many slots
-#define G2N_MIN_GROUPS 1024
-#endif
-#ifndef G2N_PTILE_SMALL_DIV  // partition blocks below 2^24 elements: kPartTile / this many (C2: 8 and 4 alike, 2 slower)
-#define G2N_PTILE_SMALL_DIV 4
-#endif
-#ifndef G2N_FORK_EARLY  // experiment builds: 1 = the deferred side work forked before the partition
-#define G2N_FORK_EARLY 0
-#endif
-#ifndef G2N_F2_OVERLAP  // bucket finish: F1 / F2 in this many bucket ranges, F2 of one beside F1 of the next (1: off)
-#define G2N_F2_OVERLAP 4
-#endif
-#ifndef G2N_FIN_DIRECT  // bucket finish: 1 = F1 places its entries (look-back; measured slower), 0 = F1 stages + F2
-#define G2N_FIN_DIRECT 0
-#endif
-
-#ifndef G2N_K2_PERSIST  // experiment builds: 1 = the persistent parse, next tile in registers (k_tile_lean_p)
-#define G2N_K2_PERSIST 0
-#endif
+constexpr uint64_t kMinGroups = 1024;   // group slots: fewer tiles per slot until the input has about this many slots
+constexpr uint32_t kPtileSmallDiv = 4;  // partition blocks below 2^24 elements: kPartTile / this many (C2: 8 and 4 alike, 2 slower)
+constexpr uint32_t kF2Ranges = 4;       // bucket finish: F1 / F2 in this many bucket ranges, F2 of one beside F1 of the next
 // options.test_flags (tests only; include/g2n.h G2N_TEST_*): take a path that is normally rare, same results
 constexpr uint32_t kTestNoBuckets = G2N_TEST_NO_BUCKETS;
 constexpr uint32_t kTestNoLean = G2N_TEST_NO_LEAN;
@@ -135,7 +110,6 @@ struct g2n_context {
   hipStream_t place = nullptr;  // F2 (k_sym_place) of earlier bucket ranges beside F1 of later ones
   hipEvent_t ov_ev[17] = {};    // F1 range k done (main -> place); [16]: place -> main join
   bool side_pending = false;    // the main stream has not joined the side stream's last work yet
-  uint64_t lean_blocks = 0;     // k_tile_lean_p blocks resident on the device at once (its grid)
   bool range_has_s = false;     // g2n_build_decimal_range: the range's evidence (k_tile_lean_evidence)
   int64_t range_d = -1;
   uint64_t range_vmax = 0;
@@ -229,6 +203,21 @@ static inline unsigned grid_for(uint64_t n, unsigned tpb = kTPB) {
   uint64_t g = (n + tpb - 1) / tpb;
   return (unsigned)(g ? g : 1);
 }
+
+#if defined(G2N_K2_STAMPS) || defined(G2N_F1_STAMPS)
+// diagnostics builds only: the n stamps at `stamps` (device) to the file the environment variable names
+static void stamps_to_file(g2n_context* c, const char* env, const unsigned long long* stamps, uint64_t n) {
+  const char* out = std::getenv(env);
+  if (!out) return;
+  std::vector<unsigned long long> h(n);
+  G2N_HIP(hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  if (FILE* f = std::fopen(out, "wb")) {
+    std::fwrite(h.data(), 8, h.size(), f);
+    std::fclose(f);
+  }
+}
+#endif
 
 static void phase(g2n_context* c, const char* name) {
   if (c->n_ev >= G2N_MAX_PHASES) return;
@@ -455,7 +444,6 @@ template <class T>
 static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* cols, uint64_t n_trip, uint64_t n_rows,
                           bool sum, g2n_result* R, const int32_t* t_rows = nullptr, const int32_t* t_cols = nullptr,
                           uint64_t n_t = 0, int64_t row_base = 0) {
-  if (G2N_FORK_EARLY) fork_side(c);  // experiment: the side work beside the partition passes
   const bool pair = t_rows != nullptr || row_base != 0;  // one element per entry of two streams
   const int bits = bits_for(n_rows);
   const double per_row =
@@ -494,7 +482,7 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
   const bool words = !t_rows && (sum || !pair);  // passes 1 and 4 (not the two-stream slices' pass 3)
   // elements per partition block: a quarter tile below 2^24 elements, so a small input still spreads
   // over more blocks than the 256 CUs
-  const uint32_t ptile = n_el >= (1ull << 24) ? kPartTile : kPartTile / G2N_PTILE_SMALL_DIV;
+  const uint32_t ptile = n_el >= (1ull << 24) ? kPartTile : kPartTile / kPtileSmallDiv;
   src.tile = ptile;
   const uint64_t n_blk1 = grouped ? c->gcoo.n_groups : (n_el + ptile - 1) / ptile;
   const uint64_t nm1 = (uint64_t)n_dig1 * n_blk1;  // one stream's count matrix
@@ -608,72 +596,44 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
   G2N_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g2n_f1_stamps), &f1st, sizeof(f1st), 0, hipMemcpyHostToDevice,
                                  c->stream));
 #endif
-  fork_side(c);  // F1 leaves HBM bandwidth to spare (G2N_FORK_EARLY: forked before pass 1 instead)
-#if G2N_FIN_DIRECT
-  // F1 places every bucket's entries itself, its offset from a decoupled look-back over the buckets
-  auto* lbst = dget<uint64_t>(c, S_FINLB, n_bk);
-  G2N_HIP(hipMemsetAsync(lbst, 0, n_bk * sizeof(uint64_t), c->stream));
-  if (sum)
-    hipLaunchKernelGGL((k_sym_finish<T, true, true>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream, el,
-                       (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl, lbst,
-                       indices, odata, (uint32_t)row_base, wa, (const uint32_t*)bstA, 0u);
-  else
-    hipLaunchKernelGGL((k_sym_finish<T, false, true>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream, el,
-                       (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl, lbst,
-                       indices, odata, (uint32_t)row_base, wa, (const uint32_t*)bstA, 0u);
-#ifdef G2N_F1_STAMPS
-  if (const char* out = std::getenv("G2N_F1_STAMPS_OUT")) {  // diagnostics build only
-    std::vector<unsigned long long> h(n_bk * kF1Stamps);
-    G2N_HIP(hipMemcpyAsync(h.data(), f1st, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    if (FILE* f = std::fopen(out, "wb")) {
-      std::fwrite(h.data(), 8, h.size(), f);
-      std::fclose(f);
-    }
-  }
-#endif
-  sync_ctl(c);
-  if (c->h_ctl->bucket_overflow) return false;
-  const int32_t nnz = read_dev(c, indptr + n_rows);
-#else
+  fork_side(c);  // F1 leaves HBM bandwidth to spare
   // F1 / F2 overlapped by bucket ranges: F1 of range k + 1 on the main stream runs beside the scan and
   // F2 of range k on the place stream (F1 is latency-bound, F2 a copy that F1 leaves bandwidth for);
   // F2 adds the entries of the ranges before its own to the range-relative offsets
   // (large builds only: on C2's 3.9K buckets the extra launches cost more than the overlap gives,
   // 0.455 -> 0.549 ms per build)
-  const uint32_t n_ov = (G2N_F2_OVERLAP > 1 && n_el <= 0x7FFFFFFFull && !(c->test_flags & kTestIndex64) &&
-                         n_bk >= 32768ull)
-                            ? (uint32_t)std::min(G2N_F2_OVERLAP, 16)
-                            : 1u;
+  const uint32_t n_ov = (n_el <= 0x7FFFFFFFull && !(c->test_flags & kTestIndex64) && n_bk >= 32768ull) ? kF2Ranges : 1u;
   // range k: buckets [rb(k), rb(k + 1)), equal ranges (ranges shrinking geometrically, so that the last F2
   // is shorter, measured slower: 70 % steps over 4 or 6 ranges, 55 % over 4, +0.06-0.18 ms per C4 build)
   auto rb = [&](uint32_t k) -> uint64_t { return n_bk * k / n_ov; };
+  uint32_t* boff = nullptr;  // the buckets' CSR offsets (relative to their range's first entry when n_ov > 1)
+  auto launch_f1 = [&](uint64_t b0, uint64_t nb) {  // F1 of buckets [b0, b0 + nb), main stream
+    auto* f1 = sum ? k_sym_finish<T, true> : k_sym_finish<T, false>;
+    hipLaunchKernelGGL(f1, dim3((unsigned)nb), dim3(kFinTPB), 0, c->stream, el, (const uint32_t*)bst, (uint32_t)low,
+                       n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl, (uint32_t)row_base, wa, (const uint32_t*)bstA,
+                       (uint32_t)b0);
+  };
+  // F2 of buckets [b0, b0 + nb) on stream st; rt[0 .. rk): the entries of the bucket ranges before them
+  auto launch_f2 = [&](hipStream_t st, auto* ind, int64_t* ip64, uint64_t b0, uint64_t nb, const uint32_t* rt,
+                       uint32_t rk) {
+    using I = std::remove_pointer_t<decltype(ind)>;
+    hipLaunchKernelGGL((k_sym_place<T, I>), dim3((unsigned)nb), dim3(kFinTPB), 0, st, (const uint32_t*)bst,
+                       (const uint32_t*)btot, (const uint32_t*)boff, (uint32_t)low, n_rows, (T)1, (const uint32_t*)tcol,
+                       (const uint16_t*)tcn, indptr, ind, odata, ip64, (const uint32_t*)bstA, (uint32_t)b0, rt, rk);
+  };
   if (n_ov > 1) {
-    auto* boff = dget<uint32_t>(c, S_MOFF, n_bk + 1);
+    boff = dget<uint32_t>(c, S_MOFF, n_bk + 1);
     auto* rtot = dget<uint32_t>(c, S_RTOT, n_ov);
     (void)dget<unsigned long long>(c, S_SCANST2, scan_tiles(n_bk) + 1);  // sized once, before the ranges' scans
     for (uint32_t k = 0; k < n_ov; k++) {
-      const uint64_t b0 = rb(k), b1 = rb(k + 1);
-      if (sum)
-        hipLaunchKernelGGL((k_sym_finish<T, true, false>), dim3((unsigned)(b1 - b0)), dim3(kFinTPB), 0, c->stream, el,
-                           (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl,
-                           (uint64_t*)nullptr, (int32_t*)nullptr, (T*)nullptr, (uint32_t)row_base, wa,
-                           (const uint32_t*)bstA, (uint32_t)b0);
-      else
-        hipLaunchKernelGGL((k_sym_finish<T, false, false>), dim3((unsigned)(b1 - b0)), dim3(kFinTPB), 0, c->stream,
-                           el, (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl,
-                           (uint64_t*)nullptr, (int32_t*)nullptr, (T*)nullptr, (uint32_t)row_base, wa,
-                           (const uint32_t*)bstA, (uint32_t)b0);
+      launch_f1(rb(k), rb(k + 1) - rb(k));
       G2N_HIP(hipEventRecord(c->ov_ev[k], c->stream));
     }
     for (uint32_t k = 0; k < n_ov; k++) {
       const uint64_t b0 = rb(k), b1 = rb(k + 1);
       G2N_HIP(hipStreamWaitEvent(c->place, c->ov_ev[k], 0));
       scan_excl<uint32_t, uint32_t>(c, (const uint32_t*)(btot + b0), boff + b0, b1 - b0, rtot + k, c->place, S_SCANST2);
-      hipLaunchKernelGGL((k_sym_place<T, int32_t>), dim3((unsigned)(b1 - b0)), dim3(kFinTPB), 0, c->place,
-                         (const uint32_t*)bst, (const uint32_t*)btot, (const uint32_t*)boff, (uint32_t)low, n_rows,
-                         (T)1, (const uint32_t*)tcol, (const uint16_t*)tcn, indptr, indices, odata, (int64_t*)nullptr,
-                         (const uint32_t*)bstA, (uint32_t)b0, (const uint32_t*)rtot, k);
+      launch_f2(c->place, indices, nullptr, b0, b1 - b0, rtot, k);
     }
     G2N_HIP(hipEventRecord(c->ov_ev[16], c->place));
     G2N_HIP(hipStreamWaitEvent(c->stream, c->ov_ev[16], 0));
@@ -691,28 +651,11 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
     phase(c, sum ? "csr" : "maxsym");
     return true;
   }
-  if (sum)
-    hipLaunchKernelGGL((k_sym_finish<T, true, false>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream, el,
-                       (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl,
-                       (uint64_t*)nullptr, (int32_t*)nullptr, (T*)nullptr, (uint32_t)row_base, wa,
-                       (const uint32_t*)bstA, 0u);
-  else
-    hipLaunchKernelGGL((k_sym_finish<T, false, false>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream, el,
-                       (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl,
-                       (uint64_t*)nullptr, (int32_t*)nullptr, (T*)nullptr, (uint32_t)row_base, wa,
-                       (const uint32_t*)bstA, 0u);
+  launch_f1(0, n_bk);
 #ifdef G2N_F1_STAMPS
-  if (const char* out = std::getenv("G2N_F1_STAMPS_OUT")) {  // diagnostics build only
-    std::vector<unsigned long long> h(n_bk * kF1Stamps);
-    G2N_HIP(hipMemcpyAsync(h.data(), f1st, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    if (FILE* f = std::fopen(out, "wb")) {
-      std::fwrite(h.data(), 8, h.size(), f);
-      std::fclose(f);
-    }
-  }
+  stamps_to_file(c, "G2N_F1_STAMPS_OUT", f1st, n_bk * kF1Stamps);
 #endif
-  auto* boff = dget<uint32_t>(c, S_MOFF, n_bk + 1);
+  boff = dget<uint32_t>(c, S_MOFF, n_bk + 1);
   scan_excl<uint32_t, uint32_t>(c, btot, boff, n_bk, boff + n_bk);
   // (an overflowed bucket is found after F2: its placement is then dropped with the rest)
   if (n_el > 0x7FFFFFFFull || (c->test_flags & kTestIndex64)) {
@@ -732,10 +675,7 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
     if (pair) throw Failure(G2N_E_UNSUPPORTED, "a sharded row slice of more than 2^31-1 entries");
     auto* indptr64 = dget<int64_t>(c, S_INDPTR64, n_rows + 1);
     auto* indices64 = dget<int64_t>(c, S_INDICES64, n_el);
-    hipLaunchKernelGGL((k_sym_place<T, int64_t>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream,
-                       (const uint32_t*)bst, (const uint32_t*)btot, (const uint32_t*)boff, (uint32_t)low, n_rows, (T)1,
-                       (const uint32_t*)tcol, (const uint16_t*)tcn, indptr, indices64, odata, indptr64,
-                       (const uint32_t*)bstA, 0u, (const uint32_t*)nullptr, 0u);
+    launch_f2(c->stream, indices64, indptr64, 0, n_bk, nullptr, 0u);
     R->format = G2N_FMT_CSR;
     R->index_width = 8;
     R->indptr = indptr64;
@@ -747,15 +687,11 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
     phase(c, sum ? "csr" : "maxsym");
     return true;
   }
-  hipLaunchKernelGGL((k_sym_place<T, int32_t>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream,
-                     (const uint32_t*)bst, (const uint32_t*)btot, (const uint32_t*)boff, (uint32_t)low, n_rows, (T)1,
-                     (const uint32_t*)tcol, (const uint16_t*)tcn, indptr, indices, odata, (int64_t*)nullptr,
-                     (const uint32_t*)bstA, 0u, (const uint32_t*)nullptr, 0u);
+  launch_f2(c->stream, indices, nullptr, 0, n_bk, nullptr, 0u);
   int32_t nnz = 0;  // one wait for the overflow flag and the entry count
   G2N_HIP(hipMemcpyAsync(&nnz, indptr + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   sync_ctl(c);
   if (c->h_ctl->bucket_overflow) return false;
-#endif
   R->format = G2N_FMT_CSR;
   R->indptr = indptr;
   R->nnz = (int64_t)nnz;
@@ -804,7 +740,7 @@ static bool csr_partition_w(g2n_context* c, const int32_t* rows, const int32_t* 
   PartSrc src{(const uint32_t*)rows, (const uint32_t*)cols, n_trip, 1u, nullptr, nullptr, 0, 0, nullptr, nullptr,
               nullptr, 0, nullptr, 0, (uint32_t)low + 1u, enc, nullptr};
   // pass 5: the entries with their values, adjacent transposed twins of one value as one element
-  const uint32_t ptile = n_el >= (1ull << 24) ? kPartTile : kPartTile / G2N_PTILE_SMALL_DIV;  // as csr_partition
+  const uint32_t ptile = n_el >= (1ull << 24) ? kPartTile : kPartTile / kPtileSmallDiv;  // as csr_partition
   src.tile = ptile;
   const bool grouped = c->gcoo.active;  // (with the parse's codes: run_build) one block per group slot
   if (grouped) {
@@ -868,15 +804,7 @@ static bool csr_partition_w(g2n_context* c, const int32_t* rows, const int32_t* 
   hipLaunchKernelGGL((k_sumw_finish<T>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream, el, ew,
                      (const uint32_t*)bst, (uint32_t)low, n_rows, btot, tcol, tval, indptr, c->ctl);
 #ifdef G2N_F1_STAMPS
-  if (const char* out = std::getenv("G2N_F1_STAMPS_OUT")) {  // diagnostics build only
-    std::vector<unsigned long long> h(n_bk * kF1Stamps);
-    G2N_HIP(hipMemcpyAsync(h.data(), f1st, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    if (FILE* f = std::fopen(out, "wb")) {
-      std::fwrite(h.data(), 8, h.size(), f);
-      std::fclose(f);
-    }
-  }
+  stamps_to_file(c, "G2N_F1_STAMPS_OUT", f1st, n_bk * kF1Stamps);
 #endif
   auto* boff = dget<uint32_t>(c, S_MOFF, n_bk + 1);
   scan_excl<uint32_t, uint32_t>(c, btot, boff, n_bk, boff + n_bk);
@@ -1129,8 +1057,8 @@ static DictOut build_dictionary(g2n_context* c, const uint8_t* in, uint64_t len,
       hipLaunchKernelGGL(k_insert_round<kModeLookup>, g, b, 0, c->stream, in, len, TI, n_t, table, cap - 1,
                          max_probes, slot, tstate, round, (int)bidir, c->ctl, first, nid_in, n_first, inv_in, tid_out);
     else {
-      const dim3 gb(grid_for(n_t, kTPB * G2N_LOOKUP_BATCH));  // G2N_LOOKUP_BATCH touches per thread
-      hipLaunchKernelGGL(k_lookup_fast<G2N_LOOKUP_BATCH>, gb, b, 0, c->stream, in, len, TI, n_t, table, cap - 1,
+      const dim3 gb(grid_for(n_t, kTPB * 2));  // 2 touches per thread
+      hipLaunchKernelGGL(k_lookup_fast<2>, gb, b, 0, c->stream, in, len, TI, n_t, table, cap - 1,
                          max_probes, tstate, (int)bidir, c->ctl, nid_in, n_first, inv_in, tid_out);
     }
     phase(c, mode == kModeClaim ? "insert_claim" : "insert_lookup");
@@ -1332,7 +1260,7 @@ static bool first_segment_pattern(g2n_context* c, const uint8_t* in, uint64_t le
 
 // The lean decimal-id parse in one pass over the input, without K1: every tile parses with
 // tile-local positions, writes its COO to a slot of kTileEdgeCap edges and its own counts
-// (k_tile_parse with ParseOpts.tile_pad); one scan of those counts gives the tile bases, a check
+// (k_tile_lean with ParseOpts.tile_pad); one scan of those counts gives the tile bases, a check
 // confirms the premise across tiles (each tile's S names continue the S lines before it, no edge
 // precedes an S line, every edge key names an S line), and the slots are compacted into the
 // stream-order COO (S_ROWS / S_COLS, sized n_edges * ktrip as run_build will ask).  False when
@@ -1354,13 +1282,10 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
   // an extended build takes group slots when its only reader is the bucket partition: unweighted, or
   // a weighted SUM CSR whose codes the parse writes (xo->wenc set by the caller as a flag)
   if (xo && xo->has_wt && !xo->wenc) grouped = false;
-#if G2N_K2_OLD
-  grouped = false;  // k_tile_parse<true> writes per-tile slots only
-#endif
   // 32 tiles per group slot; a small input takes fewer, so that the partition's first pass (one block
-  // per group) still has about G2N_MIN_GROUPS blocks (C2's 3.7K tiles: 115 groups of 32 left most CUs idle)
+  // per group) still has about kMinGroups blocks (C2's 3.7K tiles: 115 groups of 32 left most CUs idle)
   uint32_t gshift = kGroupShift;
-  while (gshift > 0 && (n_tiles >> gshift) < (uint64_t)G2N_MIN_GROUPS) gshift--;
+  while (gshift > 0 && (n_tiles >> gshift) < kMinGroups) gshift--;
   const uint64_t n_groups = (n_tiles + (1u << gshift) - 1) >> gshift;
   const uint64_t gcap = ((uint64_t)kTileEdgeCap << gshift) * ktrip;  // entries per group slot
   const uint64_t slots = grouped ? n_groups * gcap : n_tiles * kTileEdgeCap * ktrip;
@@ -1382,7 +1307,6 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
   lo.dpre = dpre;              // names behind one constant prefix (first_segment_prefixed)
   lo.dpre_len = dpre_len;
   lo.gshift = gshift;
-  lo.pf_dist = G2N_K2_PREFETCH ? (uint32_t)c->lean_blocks : 0u;
   // a whole-file build takes the unsupported-record warning itself (k_tile_lean_check); a sharded range
   // leaves it to the general protocol
   uint32_t* tunk = warn_ok ? dget<uint32_t>(c, S_TUNK, n_tiles) : nullptr;
@@ -1407,21 +1331,6 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
   G2N_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g2n_k2_stamps), &stamps, sizeof(stamps), 0, hipMemcpyHostToDevice,
                                  c->stream));
 #endif
-#if G2N_K2_OLD  // experiment builds: the k_tile_parse<true> instance
-  hipLaunchKernelGGL(k_tile_parse<true>, dim3((unsigned)n_tiles), dim3(kTPB), 0, c->stream, in, len, (const TileCnt*)nullptr,
-                     1u, 2u, lo, (uint64_t*)nullptr, (uint8_t*)nullptr, TouchOut{}, EdgeOut{}, c->ctl,
-                     (uint64_t*)nullptr, (DeferredLine*)nullptr, n_tiles, tcnt, tlean);
-#else
-#if G2N_K2_PERSIST
-  // persistent: as many blocks as fit on the device at once, each prefetching its next tile
-  const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, (uint64_t)c->lean_blocks);
-  if (grouped)
-    hipLaunchKernelGGL((k_tile_lean_p<true>), dim3(grid), dim3(kLeanTPB), 0, c->stream, in, len, lo, c->ctl, tcnt,
-                       tlean, gcount, gcap, n_tiles);
-  else
-    hipLaunchKernelGGL((k_tile_lean_p<false>), dim3(grid), dim3(kLeanTPB), 0, c->stream, in, len, lo, c->ctl, tcnt,
-                       tlean, (uint32_t*)nullptr, (uint64_t)0, n_tiles);
-#else
   if (xo && grouped)
     hipLaunchKernelGGL((k_tile_lean<kLeanDecimal, true, true>), dim3((unsigned)n_tiles), dim3(kLeanTPB), 0,
                        c->stream, in, len, lo, c->ctl, tcnt, tlean, gcount, gcap, HashLeanArgs{});
@@ -1434,19 +1343,9 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
   else
     hipLaunchKernelGGL((k_tile_lean<kLeanDecimal, false>), dim3((unsigned)n_tiles), dim3(kLeanTPB), 0, c->stream, in,
                        len, lo, c->ctl, tcnt, tlean, (uint32_t*)nullptr, (uint64_t)0, HashLeanArgs{});
-#endif
-#endif
   phase(c, "parse");
 #ifdef G2N_K2_STAMPS
-  if (const char* out = std::getenv("G2N_K2_STAMPS_OUT")) {  // diagnostics build only
-    std::vector<unsigned long long> h(n_tiles * kK2Stamps);
-    G2N_HIP(hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    if (FILE* f = std::fopen(out, "wb")) {
-      std::fwrite(h.data(), 8, h.size(), f);
-      std::fclose(f);
-    }
-  }
+  stamps_to_file(c, "G2N_K2_STAMPS_OUT", stamps, n_tiles * kK2Stamps);
 #endif
   // the tile scan, the warning's line and the premise check run unconditionally behind the parse
   // (on a failed parse their results are dropped), so the host waits once for all of them
@@ -1535,13 +1434,7 @@ static bool hash_lean_build(g2n_context* c, const uint8_t* in, uint64_t len, con
 #endif
   if (n_s == 0 || n_s >= 0x7FFFFFFFull) return false;
   uint64_t cap = 1024;
-#ifndef G2N_HL_LOAD_PCT  // experiment builds: the lean table's maximum load, percent
-#define G2N_HL_LOAD_PCT 67
-#endif
-  while (cap * G2N_HL_LOAD_PCT < n_s * 100) cap <<= 1;  // load <= 2/3: probe sequences stay short
-#ifdef G2N_HL_CAP_SHIFT  // experiment builds: table footprint vs probe cost
-  cap <<= G2N_HL_CAP_SHIFT;
-#endif
+  while (cap * 67 < n_s * 100) cap <<= 1;  // load <= 2/3: probe sequences stay short
   auto* table = dget<DictEntry>(c, S_TABLE, cap);
   G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(DictEntry), c->stream));
   auto* noff = dget<uint64_t>(c, S_NOFF, n_s);
@@ -1580,15 +1473,7 @@ static bool hash_lean_build(g2n_context* c, const uint8_t* in, uint64_t len, con
                        ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
   phase(c, "insert_lookup");
 #ifdef G2N_K2_STAMPS
-  if (const char* out = std::getenv("G2N_HL_STAMPS_OUT")) {  // diagnostics build only: the edge pass
-    std::vector<unsigned long long> h(n_tiles * kK2Stamps);
-    G2N_HIP(hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    if (FILE* f = std::fopen(out, "wb")) {
-      std::fwrite(h.data(), 8, h.size(), f);
-      std::fclose(f);
-    }
-  }
+  stamps_to_file(c, "G2N_HL_STAMPS_OUT", stamps, n_tiles * kK2Stamps);  // (the edge pass)
 #endif
   sync_ctl(c);
   if (c->h_ctl->int_fail) {
@@ -1640,15 +1525,14 @@ static bool direct_lean_build(g2n_context* c, const uint8_t* in, uint64_t len, c
                      len, ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
   hipLaunchKernelGGL(k_claim_totals, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)H.tnb, TL.n_claim,
                      &c->ctl->names_len, &c->ctl->dir_vmax);
-#if G2N_DIRECT_STORE  // (cap is a multiple of 4; the count stops past the largest claimed value)
+  // (cap is a multiple of 4; the count stops past the largest claimed value)
   G2N_HIP(hipMemsetAsync(&c->ctl->n_keep, 0, sizeof(unsigned long long), c->stream));
   hipLaunchKernelGGL(k_direct_filled, dim3((unsigned)std::min<uint64_t>(grid_for(cap / 4, 256), 2048)), dim3(256), 0,
                      c->stream, (const uint4*)direct, cap / 4, (const unsigned long long*)&c->ctl->dir_vmax,
                      &c->ctl->n_keep);
-#endif
   phase(c, "direct_claim");
   sync_ctl(c);
-  if (c->h_ctl->int_fail || (G2N_DIRECT_STORE && c->h_ctl->n_keep != n_s)) {  // (a repeated value: fewer filled)
+  if (c->h_ctl->int_fail || c->h_ctl->n_keep != n_s) {  // (a repeated value: fewer filled)
     reset_ctl(c);
     return false;
   }
@@ -1719,7 +1603,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   // coordinates only — its route or slice CSR needs no stream order)
   const bool slots_out = shard_dec && (o->range_flags & G2N_RANGE_SLOTS) && !(o->weight_tag && *o->weight_tag) && !bidir &&
                          (o->range_flags & G2N_RANGE_NO_VALUES);
-  const bool grouped = !G2N_NO_GROUP_DEFAULT && (!coo_wanted || slots_out) && !c->no_group &&
+  const bool grouped = (!coo_wanted || slots_out) && !c->no_group &&
                        !(c->test_flags & (kTestNoBuckets | kTestNoGroup));
   // bidirected keys / one integer weight tag: the extended tile-local instance (whole files only)
   const size_t wt_bytes = o->weight_tag ? std::strlen(o->weight_tag) : 0;
@@ -1756,10 +1640,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   TileLists TL;
   const bool lists_wanted = !first_one && !shard_dec;
   if (n_tiles && !local_done) {
-    if (G2N_K1_REG)
-      hipLaunchKernelGGL(k_tile_count_r, dim3((unsigned)n_tiles), dim3(kK1TPB), 0, c->stream, in, len, tps, tpe, tcnt);
-    else
-      hipLaunchKernelGGL(k_tile_count, dim3((unsigned)n_tiles), dim3(kTPB), 0, c->stream, in, len, tps, tpe, tcnt);
+    hipLaunchKernelGGL(k_tile_count_r, dim3((unsigned)n_tiles), dim3(kK1TPB), 0, c->stream, in, len, tps, tpe, tcnt);
     const uint64_t n_parts = (n_tiles + kStructChunk - 1) / kStructChunk;
     auto* part = dget<TileCnt>(c, S_TEMP, n_parts + 1);  // chunk sums, then the total
     hipLaunchKernelGGL(k_struct_reduce<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream,
@@ -1845,7 +1726,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   phase(c, "_prep");
   auto parse = [&](const ParseOpts& po) {
     if (n_tiles)
-      hipLaunchKernelGGL(k_tile_parse<false>, dim3((unsigned)n_tiles), dim3(kTPB), 0, c->stream, in, len, tbase, tps, tpe,
+      hipLaunchKernelGGL(k_tile_parse, dim3((unsigned)n_tiles), dim3(kTPB), 0, c->stream, in, len, tbase, tps, tpe,
                          po, ls, kind, T, E, c->ctl, wl, deferred, n_tiles, (TileCnt*)nullptr, (TileLean*)nullptr);
     sync_ctl(c);
     const uint64_t n_def = c->h_ctl->n_deferred;
@@ -2271,11 +2152,9 @@ static g2n_context* context_create(int device) {
   std::unique_ptr<g2n_context> c(new g2n_context());
   c->device = device;
   G2N_HIP(hipSetDevice(device));
-#ifndef G2N_SIDE_PRIO  // the side stream (names beside the finish) at the lowest priority, the pipeline at the
-#define G2N_SIDE_PRIO 1  // highest: C4 8.21-8.28 -> 8.05-8.11 ms in a same-box A/B (the names' interference 0.33 ms)
-#endif
+  // the side stream (names beside the finish) at the lowest priority, the pipeline at the highest
   int least = 0, greatest = 0;  // (no priority range: plain streams)
-  if (G2N_SIDE_PRIO && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
+  if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
     G2N_HIP(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest));
     G2N_HIP(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, least));
   } else {
@@ -2288,15 +2167,6 @@ static g2n_context* context_create(int device) {
   for (auto& e : c->ov_ev) G2N_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   G2N_HIP(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));
   if (c->n_cu <= 0) c->n_cu = 1;
-  {  // the persistent decimal parse's grid: every block resident at once (LDS-limited: 3 per CU)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tile_lean_p<true>, kLeanTPB, 0) != hipSuccess ||
-        per_cu <= 0) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    c->lean_blocks = (uint64_t)per_cu * (uint64_t)c->n_cu;
-  }
   c->bufs.resize(S_NSLOTS);
   G2N_HIP(hipMalloc(&c->ctl, sizeof(Ctl)));
   G2N_HIP(hipHostMalloc(&c->h_ctl, sizeof(Ctl), hipHostMallocDefault));

@@ -35,62 +35,29 @@
 
 namespace g2n {
 
-#ifndef G2N_PART_TPB  // experiment builds vary the partition block shape
-#define G2N_PART_TPB 1024
-#endif
-#ifndef G2N_PART_PREFETCH
-#define G2N_PART_PREFETCH 1
-#endif
-#ifndef G2N_SYM_DPP  // experiment builds: 1 = the partition / finish scans by DPP (g2n_kernels.hip) — measured
-#define G2N_SYM_DPP 0  // slower for the finish (maxsym 2.44 -> 2.54 ms on C4, same box): shuffles kept here
-#endif
-constexpr uint32_t kPartTPB = G2N_PART_TPB;       // threads of a partition block
+constexpr uint32_t kPartTPB = 1024;                // threads of a partition block
 constexpr uint32_t kSubPer = 8;                    // elements per thread in one sub-tile
 constexpr uint32_t kSub = kSubPer * kPartTPB;      // 8192 elements per sub-tile
 constexpr uint32_t kChunkSubs = 8 * 1024 / kPartTPB;  // sub-tiles per block (65536 elements)
 constexpr uint32_t kPartTile = kSub * kChunkSubs;  // 65536 elements per partition block
 constexpr uint32_t kMaxDigitBits = 10;             // LDS histogram of at most 1024 digits (the tuned shape)
 constexpr uint32_t kWideDigitBits = 11;            // pass 2 of a partition past 2^20 buckets (> 2^31 elements)
-#ifndef G2N_FIN_TPB  // experiment builds vary the finish block (one row per thread)
-#define G2N_FIN_TPB 256
-#endif
-// F1 at 8 waves per SIMD: its 106 SGPRs held it to 7; capped, 34 of them spill to VGPR lanes (VGPRs
-// stay at 62) and the C4 build gains 0.08-0.13 ms (same box, tools/gpu_r4fw8.sh).  0: uncapped.
-#ifndef G2N_FIN_W8
-#define G2N_FIN_W8 1
-#endif
-#if G2N_FIN_W8
-#define G2N_FIN_WAVES __attribute__((amdgpu_waves_per_eu(8, 8)))
-#else
-#define G2N_FIN_WAVES
-#endif
-constexpr uint32_t kFinTPB = G2N_FIN_TPB;          // threads (= rows) of a finish block
+// (F1 is compiled for 8 waves per SIMD: its 106 SGPRs held it to 7; capped, 34 of them spill to VGPR
+// lanes and the VGPRs stay at 62)
+constexpr uint32_t kFinTPB = 256;                  // threads (= rows) of a finish block
 constexpr uint32_t kSymCap = 16 * kFinTPB;         // elements one finish block holds
 constexpr uint32_t kSymPer = kSymCap / kFinTPB;    // 16 per thread
-#ifndef G2N_FIN_REG
-#define G2N_FIN_REG 8
-#endif
-constexpr uint32_t kSymReg = G2N_FIN_REG;         // stored elements per thread kept in registers
-// F1 rows at 4-word starts (a bucket whose padded rows fit kSymCap): a short row is read with four
-// ds_read_b128 instead of up to 16 lane-irregular ds_read_b32 — measured neutral on C4 (maxsym 2.427-2.441
-// against 2.442-2.444 ms, same box, round 6): the short-row reads are not what holds F1
-#ifndef G2N_F1_PAD
-#define G2N_F1_PAD 0
-#endif
+constexpr uint32_t kSymReg = 8;                    // stored elements per thread kept in registers
 
 // exclusive scan of one u32 per thread over a kN-thread block; returns the block total
 template <uint32_t kN>
 __device__ inline uint32_t block_excl_scan_n(uint32_t v, uint32_t* excl, uint32_t* lds /* >= kN / 64 */) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#if G2N_DPP_SCAN && G2N_SYM_DPP  // (g2n_kernels.hip: DPP row_shr / row_bcast, no ds_bpermute round trips)
-  const uint32_t x = wave_dpp_incl(v, 0u, dpp_add);
-#else
-  uint32_t x = v;
+  uint32_t x = v;  // (by shuffles: the DPP scans of g2n_kernels.hip measured slower for the finish)
   for (int o = 1; o < 64; o <<= 1) {
     const uint32_t y = __shfl_up(x, o, 64);
     if (lane >= o) x += y;
   }
-#endif
   if (lane == 63) lds[wid] = x;
   __syncthreads();
   uint32_t wbase = 0, tot = 0;
@@ -212,15 +179,10 @@ __device__ inline bool part_block(const PartSrc& S, uint32_t blk, PartBlock& B) 
 // Element slots per thread in one sub-tile: pass 1 loads kSubPer entries (a, b), each one or two
 // elements (kElPair) — up to 16 K elements per sub-tile, staged in 128 KB of LDS (pass 1 runs one
 // block per CU) — and expands them only when ranked, so the next sub-tile's prefetch holds the
-// entries, not the elements; the other passes load G2N_PART_EL2 elements per thread.
-#ifndef G2N_PART_EL2
-#define G2N_PART_EL2 16
-#endif
-#ifndef G2N_PART_EL4  // pass 4 (SUM twins): 16 per thread spills 124 B per lane
-#define G2N_PART_EL4 8
-#endif
+// entries, not the elements; the other passes load 16 elements per thread (pass 4, the SUM
+// twins, 8: 16 per thread spills 124 B per lane).
 template <int kPass>
-constexpr uint32_t kElPer = kPass == 1 ? 2 * kSubPer : kBase<kPass> == 4 ? G2N_PART_EL4 : kPass == 6 ? 8 : G2N_PART_EL2;
+constexpr uint32_t kElPer = kPass == 1 ? 2 * kSubPer : kBase<kPass> == 4 ? 8 : kPass == 6 ? 8 : 16;
 template <int kPass>
 constexpr uint32_t kSubEl = kElPer<kPass> * kPartTPB;  // element slots per sub-tile
 
@@ -383,15 +345,9 @@ __global__ void __launch_bounds__(kPartTPB) k_part_hist(PartSrc S, uint32_t shif
 // each of its runs front to back (whole cache lines from one L2).
 // waves per SIMD the scatter is compiled for: one 1024-thread block per CU (pass 1's stage is 128 KB;
 // two blocks per CU at 64 VGPRs spill and measured slower: 10.0 vs 9.6 ms per C4 build)
-#ifndef G2N_PART1_WAVES
-#define G2N_PART1_WAVES 4
-#endif
-#ifndef G2N_PART2_WAVES
-#define G2N_PART2_WAVES 4
-#endif
 template <int kPass, uint32_t kDB = kMaxDigitBits>
 __global__ void __launch_bounds__(kPartTPB)
-    __attribute__((amdgpu_waves_per_eu(kPass == 1 ? G2N_PART1_WAVES : G2N_PART2_WAVES)))
+    __attribute__((amdgpu_waves_per_eu(4)))
     k_part_scatter(PartSrc S, uint32_t shift, uint32_t n_dig,
                                                        const uint32_t* __restrict__ offs, uint64_t n_blk,
                                                        uint2* __restrict__ out, uint32_t* __restrict__ wout = nullptr) {
@@ -417,7 +373,7 @@ __global__ void __launch_bounds__(kPartTPB)
   constexpr uint64_t kStep = kSubEl<kPass>;
   for (uint64_t e = B.e0; e < B.e1; e += kStep) {
     for (uint32_t d = threadIdx.x; d < nd; d += kPartTPB) hist[d] = 0;
-    if (G2N_PART_PREFETCH && e + kStep < B.e1) part_fetch<kPass>(S, e + kStep, B.e1, nraw);  // next sub-tile in flight
+    if (e + kStep < B.e1) part_fetch<kPass>(S, e + kStep, B.e1, nraw);  // next sub-tile in flight
     const uint32_t valid = part_valid<kPass>(S, raw);
     __syncthreads();
     uint32_t rk[kElPer<kPass>];
@@ -474,8 +430,7 @@ __global__ void __launch_bounds__(kPartTPB)
       const uint32_t d = threadIdx.x * kDigPer + q;
       if (d < nd) cur[d] += hv[q];
     }
-    if (G2N_PART_PREFETCH) raw = nraw;
-    else if (e + kStep < B.e1) part_fetch<kPass>(S, e + kStep, B.e1, raw);
+    raw = nraw;
   }
 }
 
@@ -652,56 +607,12 @@ __device__ unsigned long long* g2n_f1_stamps;
   } while (0)
 #endif
 
-// Decoupled look-back over the buckets' status words (kDirect F1): a word holds the bucket's merged
-// entry count (kLbAgg) or the inclusive prefix through it (kLbIncl).  Written with one relaxed
-// agent-scope 8-byte store, polled with relaxed agent-scope loads (sc1: L2-served, the store drops
-// the line from its XCD's L2 — MI355X_MICROARCH.md's flag hand-off).  Every thread of the block
-// reads one predecessor per round, so a round covers kFinTPB buckets: the inclusive frontier moves
-// faster than blocks are dispatched, and a block rarely needs a second round.
-constexpr uint64_t kLbAgg = 1ull << 62, kLbIncl = 2ull << 62, kLbVal = (1ull << 62) - 1;
-
-__device__ inline uint64_t fin_lookback(uint64_t* lbst, uint64_t b, uint32_t* lb /* 4 */, uint64_t* red64 /* kFinTPB / 64 */) {
-  uint64_t acc = 0;
-  int64_t hi = (int64_t)b;
-  for (uint32_t it = 0;; it++) {
-    uint32_t* w = lb + 2 * (it & 1);  // parity-double-buffered: a thread may still read the other pair
-    if (threadIdx.x == 0) w[0] = w[1] = kFinTPB;
-    __syncthreads();
-    const int64_t j = hi - 1 - (int64_t)threadIdx.x;
-    const uint64_t st = j >= 0 ? __hip_atomic_load(lbst + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kLbIncl;
-    const uint64_t f = st >> 62;
-    if (f == 2) atomicMin(&w[0], threadIdx.x);
-    if (f == 0) atomicMin(&w[1], threadIdx.x);
-    __syncthreads();
-    const uint32_t p = w[0], z = w[1];  // nearest inclusive predecessor, nearest unpublished one
-    if (z < p) {  // block-uniform: a needed predecessor has not published yet
-      __builtin_amdgcn_s_sleep(4);
-      continue;
-    }
-    uint64_t v = threadIdx.x <= p ? (st & kLbVal) : 0ull;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red64[threadIdx.x >> 6] = v;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < kFinTPB / 64; q++) acc += red64[q];
-    __syncthreads();  // red64 is reused by the next round
-    if (p < kFinTPB) return acc;
-    hi -= kFinTPB;
-  }
-}
-
-// kDirect: the bucket's offset comes from the look-back above, and F1 writes indptr / indices /
-// data at their final place (no staging, no F2).  Otherwise F1 stages (tcol / tcn) and F2 places.
-// Measured on C4 (G2N_FIN_DIRECT, F1 stamps): the look-back costs ~10 us per block (merge + offsets
-// 1.8 -> 11.9 us: a block's window waits on predecessors dispatched to other XCDs), F1 3.56 ms
-// against 1.94 + 1.12 ms for F1 + F2 — so the staged form is the default.
-template <class T, bool kSum, bool kDirect>
-__global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint2* __restrict__ el, const uint32_t* __restrict__ bstart,
+// F1 stages the bucket's entries (tcol / tcn) and F2 (k_sym_place) places them.
+template <class T, bool kSum>
+__global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8, 8))) k_sym_finish(const uint2* __restrict__ el, const uint32_t* __restrict__ bstart,
                                                      uint32_t low, uint64_t n_rows, T one, uint32_t* __restrict__ btot,
                                                      uint32_t* __restrict__ tcol, uint16_t* __restrict__ tcn,
-                                                     int32_t* __restrict__ indptr, Ctl* ctl, uint64_t* __restrict__ lbst,
-                                                     int32_t* __restrict__ indices, T* __restrict__ data,
-                                                     uint32_t row_base, const uint32_t* __restrict__ wa,
+                                                     int32_t* __restrict__ indptr, Ctl* ctl, uint32_t row_base, const uint32_t* __restrict__ wa,
                                                      const uint32_t* __restrict__ bstA, uint32_t b0) {
   __shared__ __attribute__((aligned(16))) uint32_t seg[kSymCap];  // values (column << 1 | side) grouped by row; then merged columns
   __shared__ uint32_t cnt[kFinTPB];
@@ -710,8 +621,6 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   __shared__ uint16_t mlist[kFinTPB];  // the bucket's rows of kShortRow + 1 .. kMidRow entries
   __shared__ uint32_t mval[kFinTPB];   // per such row: its entries kept, then its output offset
   __shared__ uint32_t mcount;
-  __shared__ uint32_t lb[4];
-  __shared__ uint64_t red64[kFinTPB / 64];
   F1_STAMP(0);
   cnt[threadIdx.x] = 0;
   if (threadIdx.x == 0) mcount = 0;
@@ -724,8 +633,7 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   auto overflow = [&]() {  // the build's sums go through the general path
     if (threadIdx.x == 0) {
       ctl->bucket_overflow = 1;
-      if constexpr (kDirect) __hip_atomic_store(lbst + b, kLbIncl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else btot[b] = 0;
+      btot[b] = 0;
     }
   };
   if (n > kSymCap) {  // block-uniform
@@ -735,7 +643,6 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   __syncthreads();
   const uint32_t rmask = (1u << low) - 1u;
   uint32_t my, rs, nx;  // nx: the bucket's entries, kElPair elements expanded
-  bool padded = false;  // (G2N_F1_PAD) rows at 4-word starts; block-uniform
   {
     // the first kSymReg elements per thread stay in registers from the count to the placement;
     // a bucket of more stored elements (rare: a skewed bucket) reads the rest again, so F1 keeps
@@ -788,18 +695,7 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
     __syncthreads();
     F1_STAMP(1);
     my = cnt[threadIdx.x];
-    if constexpr (G2N_F1_PAD && !kDirect) {
-      // one scan of both layouts: the entries (low 16 bits, nx <= 2 kSymCap) and the rows rounded up
-      // to 4 words (high 16 bits); the padded layout when it fits
-      const uint32_t pm = (my + 3u) & ~3u;
-      uint32_t ex;
-      const uint32_t both = block_excl_scan_n<kFinTPB>(my | (pm << 16), &ex, red);
-      nx = both & 0xFFFFu;
-      padded = (both >> 16) <= kSymCap;
-      rs = padded ? ex >> 16 : ex & 0xFFFFu;
-    } else {
-      nx = block_excl_scan_n<kFinTPB>(my, &rs, red);
-    }
+    nx = block_excl_scan_n<kFinTPB>(my, &rs, red);
     if (nx > kSymCap) {  // block-uniform
       overflow();
       return;
@@ -833,35 +729,11 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   const uint32_t n_mid = mcount;  // block-uniform
   // short rows: registers; sorted ascending, padding sorts last
   uint32_t k[kShortRow];
-  if constexpr (G2N_F1_PAD && !kDirect) {
-    if (padded) {
 #pragma unroll
-      for (uint32_t q4 = 0; q4 < kShortRow / 4; q4++) {
-        uint4 v = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-        if (live && shortrow && 4 * q4 < my) v = *reinterpret_cast<const uint4*>(sg + 4 * q4);
-        k[4 * q4] = v.x;
-        k[4 * q4 + 1] = v.y;
-        k[4 * q4 + 2] = v.z;
-        k[4 * q4 + 3] = v.w;
-      }
-#pragma unroll
-      for (uint32_t q = 0; q < kShortRow; q++)
-        if (!(live && shortrow && q < my)) k[q] = 0xFFFFFFFFu;
-    } else {
-#pragma unroll
-      for (uint32_t q = 0; q < kShortRow; q++) k[q] = (live && shortrow && q < my) ? sg[q] : 0xFFFFFFFFu;
-    }
-  } else {
-#pragma unroll
-    for (uint32_t q = 0; q < kShortRow; q++) k[q] = (live && shortrow && q < my) ? sg[q] : 0xFFFFFFFFu;
-  }
+  for (uint32_t q = 0; q < kShortRow; q++) k[q] = (live && shortrow && q < my) ? sg[q] : 0xFFFFFFFFu;
   {  // one network per wave: the longest short row of the wave picks it (no divergent sorts)
     uint32_t wm = (live && shortrow) ? my : 0u;
-#if G2N_DPP_SCAN && G2N_SYM_DPP
-    wm = wave_dpp_reduce(wm, 0u, dpp_max);
-#else
     for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor(wm, o, 64));
-#endif
     if (wm > 8) net_sort<16>(k);
     else if (wm > 4) net_sort<8>(k);
     else if (wm > 1) net_sort<4>(k);
@@ -935,23 +807,9 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   }
   F1_STAMP(3);
   const uint32_t m = !live ? 0u : (shortrow ? short_merge() : midrow ? mval[threadIdx.x] : long_merge(none));
-  // kDirect: a short row's sorted values go back to its own segment (nobody else reads or writes it
-  // before the staging below), so k[] need not stay in registers across the look-back
-  if (kDirect && live && shortrow) {
-#pragma unroll
-    for (uint32_t q = 0; q < kShortRow; q++)
-      if (q < my) sg[q] = k[q];
-  }
   uint32_t off;
   const uint32_t tot = block_excl_scan_n<kFinTPB>(m, &off, red);
-  uint64_t base = 0;  // kDirect: the bucket's first CSR entry
-  if constexpr (kDirect) {
-    if (threadIdx.x == 0) __hip_atomic_store(lbst + b, kLbAgg | tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    base = fin_lookback(lbst, b, lb, red64);
-    if (threadIdx.x == 0) __hip_atomic_store(lbst + b, kLbIncl | (base + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    if (threadIdx.x == 0) btot[b] = tot;
-  }
+  if (threadIdx.x == 0) btot[b] = tot;
   F1_STAMP(4);
   // tot <= nx <= 2 n: the bucket's staged entries stay inside [2 e0, 2 e0 + 2 n).  A staged entry is
   // its column with bit 31 set when its value sums more than one copy (columns < 2^30); only then
@@ -959,30 +817,16 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   uint32_t* ocol = tcol + 2 * (uint64_t)e0;
   uint16_t* ocn = tcn + 2 * (uint64_t)e0;
   auto stage = [&](uint32_t j, uint32_t c, uint32_t kk) -> uint32_t {  // entry j of the bucket, staged
-    if (kk > 1u) {
-      if constexpr (kDirect) data[base + j] = sum_copies<T>(one, kk);
-      else ocn[j] = (uint16_t)kk;
-    }
+    if (kk > 1u) ocn[j] = (uint16_t)kk;
     return kk > 1u ? (c | kMultiCopy) : c;
   };
-  auto out = [&](uint32_t j, uint32_t c, uint32_t kk) {  // entry j of the bucket, straight out
-    if constexpr (kDirect) {
-      indices[base + j] = (int32_t)c;
-      data[base + j] = sum_copies<T>(one, kk);
-    } else {
-      ocol[j] = stage(j, c, kk);
-    }
-  };
+  auto out = [&](uint32_t j, uint32_t c, uint32_t kk) { ocol[j] = stage(j, c, kk); };  // ... straight out
   if (live) {
-    indptr[row] = (int32_t)(base + off);  // !kDirect: local, k_sym_place adds the bucket's offset
-    if (row == n_rows - 1) indptr[n_rows] = (int32_t)(base + off + m);
+    indptr[row] = (int32_t)off;  // local: k_sym_place adds the bucket's offset
+    if (row == n_rows - 1) indptr[n_rows] = (int32_t)(off + m);
     if (longrow)  // straight out, before the staging below reuses the segments
       long_merge([&](uint32_t j, uint32_t c, uint32_t kk) { out(off + j, c, kk); });
     if (midrow) mval[threadIdx.x] = off;
-  }
-  if constexpr (kDirect) {
-#pragma unroll
-    for (uint32_t q = 0; q < kShortRow; q++) k[q] = (live && shortrow && q < my) ? sg[q] : 0xFFFFFFFFu;
   }
   __syncthreads();  // every segment read before the staging below overwrites them
   if (n_mid) {  // the wave-sorted rows, straight out (consecutive lanes write consecutive entries)
@@ -1011,12 +855,7 @@ __global__ void __launch_bounds__(kFinTPB) G2N_FIN_WAVES k_sym_finish(const uint
   for (uint32_t i = threadIdx.x; i < tot; i += kFinTPB) {
     const uint32_t c = seg[i];
     if (c == kStagedSkip) continue;
-    if constexpr (kDirect) {
-      indices[base + i] = (int32_t)(c & ~kMultiCopy);
-      if (!(c & kMultiCopy)) data[base + i] = sum_copies<T>(one, 1u);
-    } else {
-      ocol[i] = c;
-    }
+    ocol[i] = c;
   }
 #ifdef G2N_F1_STAMPS
   F1_STAMP(6);
@@ -1048,10 +887,7 @@ __global__ void __launch_bounds__(kFinTPB) k_sym_place(const uint32_t* __restric
   const uint32_t e0 = bstart[b] + (bstA ? bstA[b] : 0u), tot = btot[b], base = boff[b] + rbase;
   const uint32_t* src = tcol + 2 * (uint64_t)e0;
   const uint16_t* scn = tcn + 2 * (uint64_t)e0;
-#ifndef G2N_PLACE_U
-#define G2N_PLACE_U 8
-#endif
-  constexpr uint32_t kU = G2N_PLACE_U;  // loads in flight per thread (a bucket averages ~1500 entries)
+  constexpr uint32_t kU = 8;  // loads in flight per thread (a bucket averages ~1500 entries)
   for (uint32_t i0 = threadIdx.x; i0 < tot; i0 += kU * kFinTPB) {
     uint32_t c[kU];
 #pragma unroll
@@ -1158,9 +994,7 @@ __device__ inline void sumw_sort_row(unsigned long long* seg, uint32_t n) {
   }
 }
 
-#ifndef G2N_F1W_MID  // experiment builds: the longest row F1w sorts by a whole wave (16: none)
-#define G2N_F1W_MID 64
-#endif
+constexpr uint32_t kF1wMid = 64;  // the longest row F1w sorts by a whole wave
 // F1w: one block per bucket of 2^low <= kFinTPB rows (thread = row): the bucket's entries (a kElPair
 // element is the twins (a, b) and (b, a) of one value) grouped by row as (column << 32 | value) in
 // LDS, each row sorted by its lane, its column runs summed; the merged entries staged at twice the
@@ -1249,8 +1083,8 @@ __global__ void __launch_bounds__(kFinTPB) k_sumw_finish(const uint2* __restrict
   // ones by their lane in LDS
   constexpr int kR = 16;
   const bool inreg = my <= (uint32_t)kR;
-  const bool midrow = live && !inreg && my <= G2N_F1W_MID;
-  const bool longrow = live && my > G2N_F1W_MID;
+  const bool midrow = live && !inreg && my <= kF1wMid;
+  const bool longrow = live && my > kF1wMid;
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (midrow) mlist[atomicAdd(&mcount, 1u)] = (uint16_t)threadIdx.x;
   unsigned long long r[kR];
@@ -1258,11 +1092,7 @@ __global__ void __launch_bounds__(kFinTPB) k_sumw_finish(const uint2* __restrict
   for (int i = 0; i < kR; i++) r[i] = (live && inreg && i < (int)my) ? sg[i] : ~0ull;  // padding sorts last
   {  // one network per wave: the longest in-register row of the wave picks it (no divergent sorts)
     uint32_t wm = (live && inreg) ? my : 0u;
-#if G2N_DPP_SCAN && G2N_SYM_DPP
-    wm = wave_dpp_reduce(wm, 0u, dpp_max);
-#else
     for (int o = 32; o > 0; o >>= 1) wm = max(wm, (uint32_t)__shfl_xor(wm, o, 64));
-#endif
     if (wm > 8) sumw_sort_net<16>(r);
     else if (wm > 4) sumw_sort_net<8>(r);
     else if (wm > 1) sumw_sort_net<4>(r);

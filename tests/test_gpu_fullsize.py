@@ -77,6 +77,7 @@ def _device_build(n_s, n_l, names="decimal", **opts):
         assert rc == 0, (nat.status_name(rc), nat.last_error())
         n, nnz = int(res.n_nodes), int(res.nnz)
         out = {"n": n, "nnz": nnz, "format": res.format, "n_edges": int(res.n_edges)}
+        out["phases"] = [res.phase_names[k].decode() for k in range(res.n_phases)]
         if res.format == nat.FMT_CSR:
             out["indptr"] = _down(hip, res.indptr, n + 1, np.int32)
             out["indices"] = _down(hip, res.indices, nnz, np.int32)
@@ -182,6 +183,22 @@ def test_c4_prefixed_names_full_size_equals_oracle(gpu):
     assert out["format"] == nat.FMT_CSR and out["n"] == d["n_nodes"] and out["nnz"] == d["parse"]["nnz"]
     assert _digest(out["indptr"], out["indices"], out["data"]) == d["parse"]["digest"]
     assert hashlib.sha256(out["blob"].tobytes()).hexdigest() == d["names"]
+
+
+def test_maxsym_finish_by_bucket_ranges_equals_row_sum_path(gpu):
+    """The bucket finish overlapped by ranges (F1 of range k + 1 beside the scan and F2 of range k) needs
+    32 768 buckets; 2^23 rows at 0.25 elements per row (buckets of 256 rows) is the smallest shape with
+    that many, so the finish runs in 4 bucket ranges.  Equal to the general row-sum path
+    (TEST_NO_BUCKETS), which the goldens pin to the oracle."""
+    from gfa2network_amd import _native as nat
+
+    got = _device_build(1 << 23, 1 << 20, output=nat.OUT_PARSE)
+    want = _device_build(1 << 23, 1 << 20, output=nat.OUT_PARSE, test_flags=nat.TEST_NO_BUCKETS)
+    assert "maxsym" in got["phases"], got["phases"]
+    assert got["format"] == want["format"] == nat.FMT_CSR
+    assert got["n"] == want["n"] == 1 << 23 and got["nnz"] == want["nnz"]
+    for k in ("indptr", "indices", "data"):
+        assert np.array_equal(got[k], want[k]), k
 
 
 def test_c5_single_gpu_properties(gpu):

@@ -1,11 +1,10 @@
-"""Analyse the K2 (k_tile_parse<true>) phase stamps of a -DG2N_K2_STAMPS build.
+"""Analyse the K2 (k_tile_lean) phase stamps of a -DG2N_K2_STAMPS build.
 
 usage: python tools/k2_stamps.py stamps.bin [out.json] [f1]
 (f1: the bucket-finish stamps of a -DG2N_F1_STAMPS build: 0 entry, 1 loaded + counted, 2 placed,
 3 rows sorted, 4 merged + offsets, 5 staged, 6 end; 9 = hardware id)
-stamps.bin: n_tiles x 10 u64 — wall clock (100 MHz) at: 0 entry, 1 staged, 2 chunk masks,
-3 chunk-rank scan, 4 start list, 5 kinds + line prefixes, 6 thread 0's lines parsed, 7 all lines
-parsed (barrier), 8 end; 9 = XCC id << 32 | HW_ID.
+stamps.bin: n_tiles x 10 u64 — wall clock (100 MHz) at: 0 entry, 1 staged + bitmaps, 2 starts
+classified, 3 block scan, 4 line records, 5 lines parsed, 6 end; 9 = XCC id << 32 | HW_ID.
 Prints per-segment mean / median block time, the kernel span, the average number of blocks
 resident per CU over the span, and the idle time between consecutive blocks on a CU.
 """
@@ -14,7 +13,6 @@ import sys
 
 import numpy as np
 
-NAMES = ["stage", "masks", "scan", "starts", "classify", "parse_t0", "parse_all", "finish"]
 TICK_NS = 10.0  # wall_clock64 at 100 MHz
 
 
@@ -25,9 +23,7 @@ F1_NAMES = ["load_count", "place", "sort", "merge_scan", "stage", "write"]
 def main():
     a = np.fromfile(sys.argv[1], dtype=np.uint64).reshape(-1, 10)
     a = a[a[:, 0] != 0]  # tiles that returned before the first stamp (the hash passes skip some)
-    lean = bool((a[:, 7] == 0).all())  # k_tile_lean stamps 0..6 (and the hardware id in 9)
-    names = LEAN_NAMES if lean else NAMES
-    last = 6 if lean else 8
+    names, last = LEAN_NAMES, 6  # stamps 0..6 (and the hardware id in 9)
     if len(sys.argv) > 3 and sys.argv[3] == "f1":
         names, last = F1_NAMES, 6
     t = a[:, :last + 1].astype(np.int64)
