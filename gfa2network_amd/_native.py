@@ -40,6 +40,7 @@ EXPORTED = [
     "g2n_context_group_slots", "g2n_route_group_slots", "g2n_csr_from_group_slots",
     "g2n_keyset_create", "g2n_keyset_add", "g2n_keyset_view", "g2n_keyset_free",
     "g2n_gunzip", "g2n_gunzip_chunked", "g2n_free", "g2n_split_render", "g2n_split_get", "g2n_split_segments", "g2n_split_free", "g2n_join_names", "g2n_gather_names", "g2n_write_npz", "g2n_write_node_map", "g2n_first_bad_utf8",
+    "g2n_csr_stats", "g2n_csr_stats_host", "g2n_stats_from_path",
 ]
 
 
@@ -130,6 +131,20 @@ class Result(ctypes.Structure):
         ("host_ms_h2d", ctypes.c_double),
         ("host_ms_d2h", ctypes.c_double),
         ("priv_", ctypes.c_void_p),
+    ]
+
+
+class GraphStats(ctypes.Structure):
+    """g2n_graph_stats (include/g2n.h)."""
+
+    _fields_ = [
+        ("n_nodes", ctypes.c_int64),
+        ("n_entries", ctypes.c_int64),
+        ("n_diag", ctypes.c_int64),
+        ("n_components", ctypes.c_int64),
+        ("max_degree", ctypes.c_int64),
+        ("ms_degree", ctypes.c_double),
+        ("ms_components", ctypes.c_double),
     ]
 
 
@@ -288,6 +303,13 @@ def load() -> ctypes.CDLL:
     lib.g2n_keyset_view.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
     lib.g2n_keyset_free.argtypes = [P]
     lib.g2n_keyset_free.restype = None
+    lib.g2n_csr_stats.argtypes = [P, P, P, I32, U64, U64, I32, ctypes.POINTER(GraphStats)]
+    lib.g2n_csr_stats.restype = ctypes.c_int
+    lib.g2n_csr_stats_host.argtypes = [P, P, I32, U64, U64, I32, I32, ctypes.POINTER(GraphStats)]
+    lib.g2n_csr_stats_host.restype = ctypes.c_int
+    lib.g2n_stats_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), ctypes.POINTER(GraphStats),
+                                        ctypes.POINTER(I64), ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_stats_from_path.restype = ctypes.c_int
     for f in ("g2n_keyset_create", "g2n_keyset_add", "g2n_keyset_view", "g2n_partition_keys", "g2n_dedup_keys", "g2n_gather_keys", "g2n_remap_pairs", "g2n_route_triplets", "g2n_csr_from_coo_pair",
               "g2n_context_group_slots", "g2n_route_group_slots", "g2n_csr_from_group_slots",
               "g2n_upload_file_range", "g2n_count_device", "g2n_build_decimal_range", "g2n_order_keys",
@@ -442,6 +464,44 @@ def build_from_buffer(data: bytes | bytearray | memoryview | np.ndarray, opts: O
     rc = lib.g2n_build_from_buffer(arr.ctypes.data if arr.size else None, arr.size, ctypes.byref(opts),
                                    ctypes.byref(res))
     return _from_result(res, rc)
+
+
+def _stats_dict(st: GraphStats) -> dict:
+    return {"n_nodes": int(st.n_nodes), "n_entries": int(st.n_entries), "n_diag": int(st.n_diag),
+            "n_components": int(st.n_components), "max_degree": int(st.max_degree),
+            "ms_degree": float(st.ms_degree), "ms_components": float(st.ms_components)}
+
+
+def stats_from_path(path: str, opts: Options) -> tuple[RawResult, dict, int]:
+    """g2n_stats_from_path: (the build's result without a matrix, the g2n_graph_stats fields, P / O
+    records).  The statistics are meaningful only when the result's status is OK."""
+    lib = load()
+    res = ctypes.POINTER(Result)()
+    st, n_paths = GraphStats(), ctypes.c_int64(0)
+    rc = lib.g2n_stats_from_path(os.fsencode(path), ctypes.byref(opts), ctypes.byref(st), ctypes.byref(n_paths),
+                                 ctypes.byref(res))
+    return _from_result(res, rc), _stats_dict(st), int(n_paths.value)
+
+
+def csr_stats_host(indptr: np.ndarray, indices: np.ndarray, n: int, directed: bool, device: int = 0) -> dict:
+    """g2n_csr_stats_host on a host CSR's structure: indptr / indices both int32 or both int64."""
+    lib = load()
+    idt = np.dtype(indptr.dtype)
+    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
+        raise TypeError("indptr / indices must both be int32 or both int64")
+    ip, ix = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
+    if len(ip) != n + 1:
+        raise ValueError("indptr must hold n + 1 offsets")
+    st = GraphStats()
+    rc = lib.g2n_csr_stats_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, n, len(ix),
+                                int(bool(directed)), int(device), ctypes.byref(st))
+    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
+        raise NotImplementedError(f"GPU graph statistics: {last_error()}")
+    if rc == E_ARG:
+        raise ValueError(f"GPU graph statistics: {last_error()}")
+    if rc != OK:
+        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+    return _stats_dict(st)
 
 
 BAND_ENTRIES = 2**31 - 2  # entries one g2n_coo_to_csr_band call takes (the weighted row-sum path's limit)

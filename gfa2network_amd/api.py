@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz"]
+           "save_npz", "compute_stats", "graph_stats", "density"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
 # build's device working set is at most about this many bytes per input byte (the lean decimal-id
@@ -725,6 +725,96 @@ def parse_gfa_names(path, *, raw_bytes_id: bool = False, **kw):
             bytes(blob[offs[bad]:offs[bad + 1]]).decode()
             raise AssertionError("decode of the reported name unexpectedly succeeded")
     return A, blob, offs
+
+
+def density(n_nodes: int, n_edges: int, directed: bool):
+    """``nx.density`` of a graph with these counts (what compute_stats reports, analysis.py:57): the
+    int 0 without edges or with at most one node, else m / (n (n - 1)), doubled when undirected —
+    from Python ints, whose true division is correctly rounded however large n (n - 1) is."""
+    n, m = int(n_nodes), int(n_edges)
+    if m == 0 or n <= 1:
+        return 0
+    d = m / (n * (n - 1))
+    if not directed:
+        d *= 2
+    return d
+
+
+def _stats_edges(st: dict, directed: bool) -> int:
+    """Edges of the nx.DiGraph / nx.Graph whose adjacency structure has these counts: every stored
+    entry, or (undirected: each edge is stored from both ends, a self-loop once) half of the entries
+    plus the diagonal."""
+    return st["n_entries"] if directed else (st["n_entries"] + st["n_diag"]) // 2
+
+
+def graph_stats(A, *, directed: bool = True, device: int = 0) -> dict:
+    """Statistics of the graph whose adjacency structure is the square scipy sparse matrix ``A``
+    (extension; the reference has no such function): ``nodes``, ``edges``, ``components``,
+    ``max_degree`` and ``density`` as ``compute_stats`` reports them for the graph ``parse_gfa(...,
+    asymmetric=True)`` describes — every stored (u, v) is an edge u -> v (``directed``) or u - v; the
+    values are never read.  Runs on the GPU over the CSR structure (g2n_csr_stats_host); a matrix in
+    another format is converted first, duplicates summed."""
+    if not sp.issparse(A):
+        raise TypeError("graph_stats takes a scipy sparse matrix")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("graph_stats takes a square matrix")
+    if A.format != "csr":
+        # structure only: unit values in a dtype whose sums cannot overflow
+        C = A.tocoo()
+        A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
+        A.sum_duplicates()
+    n = int(A.shape[0])
+    if n >= 2**31 - 1:
+        raise NotImplementedError("GPU graph statistics need node ids below 2^31 - 1")
+    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
+    st = nat.csr_stats_host(np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt), n, directed, device)
+    edges = _stats_edges(st, directed)
+    return {"nodes": st["n_nodes"], "edges": edges, "components": st["n_components"],
+            "max_degree": st["max_degree"], "density": density(st["n_nodes"], edges, directed)}
+
+
+def _stats_one_piece(path, device: int) -> None:
+    """compute_stats builds the file in one piece on one GPU: an input parse_gfa would build in
+    chunks (its working set past the GPU's free HBM) is outside it."""
+    p = str(path)
+    if not os.path.isfile(p):
+        return  # the build raises the reference's OSError
+    size = os.path.getsize(p)
+    if _chunk_plan(_gz_inflated_estimate(p, size) if p.endswith(".gz") else size, device):
+        raise NotImplementedError(
+            "compute_stats builds the graph in one piece on one GPU and this input's working set exceeds its free "
+            "HBM: build the matrix with parse_gfa(..., asymmetric=True) (chunked or sharded) and pass it to "
+            "graph_stats")
+
+
+def compute_stats(path, *, directed: bool = True, strip_orientation: bool = False, raw_bytes_id: bool = False,
+                  device: int = 0) -> dict:
+    """GPU ``compute_stats`` (gfa2network/analysis.py:33-65): ``nodes``, ``edges``, ``paths``,
+    ``components``, ``max_degree`` and ``density`` of the graph ``parse_gfa(path, build_graph=True,
+    directed=..., strip_orientation=..., raw_bytes_id=...)`` builds, in that key order, with the
+    reference's exceptions and its one-shot warning.  The file is parsed once: the asymmetric summed
+    CSR is built in HBM, the statistics are taken from it there (g2n_stats.hip) and only scalars come
+    back.  Stdin and file objects raise NotImplementedError (the reference reads its input twice, so a
+    pipe gives it no paths).  ``device`` is an extension."""
+    if hasattr(path, "read") or str(path) == "-":
+        raise NotImplementedError("compute_stats reads a named file (the reference parses its input twice)")
+    _stats_one_piece(path, device)
+    opts = nat.make_options(directed=directed, strip_orientation=strip_orientation, asymmetric=True,
+                            output=nat.OUT_CSR, want_node_names=not raw_bytes_id, device=device)
+    raw, st, n_paths = nat.stats_from_path(str(path), opts)
+    dt = np.dtype("float64")
+    if raw.status == nat.E_UNICODE and raw.err_line < 0:
+        # builders.py:155-162: the graph path decodes every node key as ASCII (the parse itself was clean)
+        if raw.has_warning:
+            warnings.warn(f"Skipping unsupported record: {chr(raw.warn_byte)}", RuntimeWarning, stacklevel=2)
+        bytes(raw.err_detail).decode("ascii")
+        raise AssertionError("decode of the reported key unexpectedly succeeded")
+    finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=raw_bytes_id, verbose=False, build_matrix=False,
+             path=path)
+    raise_for_status(raw, dt, path)
+    edges = _stats_edges(st, directed)
+    return {"nodes": st["n_nodes"], "edges": edges, "paths": n_paths, "components": st["n_components"],
+            "max_degree": st["max_degree"], "density": density(st["n_nodes"], edges, directed)}
 
 
 def _run(path, opts) -> RawResult:

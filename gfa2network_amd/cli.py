@@ -4,8 +4,9 @@ Same global flags (they precede the subcommand) and ``convert`` flags as
 gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backend, parse,
 ``convert_format``, ``save_matrix`` (dense guard -> SystemExit), then the
 ``<matrix>.nodes.tsv`` sidecar.  ``export --format edge-list`` (cli.py:264-281) renders its
-lines on the GPU from the same parse.  Graph outputs (``--graph``, export graphml / gexf /
-json) and stats / distance / distance-matrix are outside the GPU GFA->CSR path.
+lines on the GPU from the same parse; ``stats`` (cli.py:152-159, 364-376) prints
+``compute_stats``'s six numbers, taken on the GPU from the CSR.  Graph outputs (``--graph``,
+export graphml / gexf / json) and distance / distance-matrix are outside the GPU GFA->CSR path.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import sys
 from pathlib import Path
 
 from . import __version__
-from .api import convert_format, export_edge_list, parse_gfa, parse_gfa_names, save_matrix, save_node_map_native
+from .api import compute_stats, convert_format, export_edge_list, parse_gfa, parse_gfa_names, save_matrix, save_node_map_native
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -56,7 +57,13 @@ def _parser() -> argparse.ArgumentParser:
     p_exp.add_argument("--keep-directed-bidir", action="store_true",
                        help="Keep original directed bidirected behaviour")
     p_exp.add_argument("--output", help="Output path", default="-")
-    for name in ("stats", "distance", "distance-matrix"):
+    p_stats = sub.add_parser("stats", help="Print basic graph statistics", aliases=["stat"])  # cli.py:152-159
+    p_stats.add_argument("gfa", help="Input *.gfa* file")
+    g2 = p_stats.add_mutually_exclusive_group()
+    g2.add_argument("--directed", dest="directed", action="store_true", default=True)
+    g2.add_argument("--undirected", dest="directed", action="store_false")
+    p_stats.add_argument("--strip-orientation", action="store_true")
+    for name in ("distance", "distance-matrix"):
         sp_ = sub.add_parser(name, help="(outside the GPU GFA->CSR path)")
         sp_.add_argument("rest", nargs=argparse.REMAINDER)
     return parser
@@ -69,6 +76,18 @@ def main(argv: list[str] | None = None) -> None:
         if args.format != "edge-list":
             parser.error(f"export --format {args.format} builds a NetworkX graph, outside the GPU GFA->CSR path")
         export_edge_list(args.gfa, args.output, bidirected=args.bidirected, device=args.device)
+        return
+    if args.cmd == "stats":  # cli.py:364-376 (the alias reaches no branch there either)
+        stats = compute_stats(args.gfa, directed=args.directed, strip_orientation=args.strip_orientation,
+                              raw_bytes_id=args.raw_bytes_id, device=args.device)
+        print("nodes\t", stats["nodes"])
+        print("edges\t", stats["edges"])
+        print("paths\t", stats["paths"])
+        print("components\t", stats["components"])
+        print("max_degree\t", stats["max_degree"])
+        print("density\t", f"{stats['density']:.6g}")
+        return
+    if args.cmd == "stat":
         return
     if args.cmd != "convert":
         parser.error(f"'{args.cmd}' is outside the GPU GFA->CSR path; use the reference gfa2network for it")

@@ -194,11 +194,9 @@ int g2n_build_from_buffer(const void* buf, size_t len, const g2n_options* opts, 
   return g2n::guarded([&] { return g2n::build_host(buf, len, opts, out, 0.0); });
 }
 
-int g2n_build_from_path(const char* path, const g2n_options* opts, g2n_result** out) {
-  if (!out || !path) return G2N_E_ARG;
-  *out = nullptr;
-  int rc = check_opts(opts);
-  if (rc) return rc;
+// GFAParser's source selection and the build of what it read (g2n_build_from_path; g2n_stats_from_path
+// runs the same ingest with a stats request set)
+static int build_from_path(const char* path, const g2n_options* opts, g2n_result** out) {
   return g2n::guarded([&]() -> int {
     const double t0 = g2n::now_ms();
     std::string p(path);
@@ -286,6 +284,41 @@ int g2n_build_from_path(const char* path, const g2n_options* opts, g2n_result** 
     g2n::free_later(std::move(z.parts));
     return rc2;
   });
+}
+
+int g2n_build_from_path(const char* path, const g2n_options* opts, g2n_result** out) {
+  if (!out || !path) return G2N_E_ARG;
+  *out = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  return build_from_path(path, opts, out);
+}
+
+int g2n_stats_from_path(const char* path, const g2n_options* opts, g2n_graph_stats* stats, int64_t* n_paths,
+                        g2n_result** res) {
+  if (!res || !path || !stats || !n_paths) return G2N_E_ARG;
+  *res = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  std::memset(stats, 0, sizeof(*stats));
+  *n_paths = 0;
+  g2n_options o;  // the plain graph's build: the summed asymmetric CSR, whose values nobody reads
+  g2n_options_init(&o);
+  o.directed = opts->directed != 0;
+  o.strip_orientation = opts->strip_orientation != 0;
+  o.asymmetric = 1;
+  o.dtype = G2N_BOOL;
+  o.output = G2N_OUT_CSR;
+  o.want_node_names = opts->want_node_names != 0;
+  o.device = opts->device;
+  o.unknown_warned = opts->unknown_warned;
+  o.test_flags = opts->test_flags;
+  const g2n::StatsRequest req{stats, n_paths, o.directed, o.want_node_names != 0};
+  struct Scope {
+    explicit Scope(const g2n::StatsRequest* r) { g2n::set_stats_request(r); }
+    ~Scope() { g2n::set_stats_request(nullptr); }
+  } scope(&req);
+  return build_from_path(path, &o, res);
 }
 
 int g2n_upload_file_range(const char* path, uint64_t offset, uint64_t len, void* d_dst, int32_t device) {

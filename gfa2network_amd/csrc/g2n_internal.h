@@ -78,6 +78,17 @@ void staged_upload(int device, uint8_t* d, size_t len, const FillFn& fill);
 int build_host_fill(size_t len, const FillFn& fill, const g2n_options* opts, g2n_result** out, double read_ms);
 int build_host(const void* buf, size_t len, const g2n_options* opts, g2n_result** out, double read_ms);
 
+// g2n_stats_from_path: while a request is set on the calling thread, build_host_fill / build_host_bgzf
+// keep the built CSR on the device, run g2n_csr_stats on it and download the scalars only (the result
+// carries status, errors, warning and counts as ever, no matrix and no names).
+struct StatsRequest {
+  g2n_graph_stats* out;
+  int64_t* n_paths;
+  int32_t directed;
+  bool check_ascii;  // a node key with a byte >= 0x80: status G2N_E_UNICODE, err_line -1 (include/g2n.h)
+};
+void set_stats_request(const StatsRequest* req);  // nullptr: none (thread-local)
+
 // Parallel multi-member gunzip.  Members are found by their header bytes and inflated
 // speculatively on host_threads() threads; the chain of members from byte 0 (zero padding
 // between members skipped, gzip.py _read_eof) is then walked in order.  Returns false when

@@ -24,6 +24,7 @@
 #include "g2n_route.hip"
 #include "g2n_inflate.hip"
 #include "g2n_keyset.hip"
+#include "g2n_stats.hip"
 
 #define G2N_HIP(call)                                                                                      \
   do {                                                                                                     \
@@ -42,7 +43,9 @@ enum Slot {
   S_ROUT1, S_UCNT0, S_UCNT1, S_UOFF, S_MCNT, S_MOFF, S_RSCR, S_RFLAG0, S_RFLAG1, S_RVAL0, S_RVAL1, S_TID,
   S_INV, S_TUNK, S_DEFER, S_FOFF64, S_BTC, S_BTV, S_BTOT, S_EBAD, S_ELEN, S_EPOS, S_ETEXT, S_EFIRST, S_EMETA, S_EL0, S_EL1,
   S_PCNT, S_POFF, S_PGRP, S_BSTART, S_SCANST, S_RBOUND, S_ROWSP, S_COLSP, S_TLEAN, S_ZIN, S_ZMEM, S_ZBAD, S_RSK, S_RSV, S_RSCNT, S_RSOFF,
-  S_GCNT, S_TCN, S_INDPTR64, S_INDICES64, S_WENC, S_W1, S_W2, S_TVAL, S_PW0, S_PW1, S_BSTARTA, S_DIRECT, S_RTOT, S_SCANST2, S_EWP, S_TLIST, S_TNB, S_WENCP, S_NSLOTS
+  S_GCNT, S_TCN, S_INDPTR64, S_INDICES64, S_WENC, S_W1, S_W2, S_TVAL, S_PW0, S_PW1, S_BSTARTA, S_DIRECT, S_RTOT, S_SCANST2, S_EWP, S_TLIST, S_TNB, S_WENCP,
+  S_STPARENT, S_STCOL, S_STDIAG, S_STLONG, S_STOUT, S_STIP, S_STIX,  // g2n_csr_stats (g2n_stats.hip)
+  S_NSLOTS
 };
 
 constexpr uint64_t kMinGroups = 1024;   // group slots: fewer tiles per slot until the input has about this many slots
@@ -104,6 +107,8 @@ struct g2n_context {
   g2n::ScanSlot scan_slot[g2n::S_NSLOTS];  // scan_excl's per-slot epoch / ticket state
   bool edge_text = false;     // run_edge_list's build: decimal names are left to the text render
   bool names_dec = false;     // ... and that build's names were the decimal ids (no blob written)
+  bool stats_names = false;   // g2n_stats_from_path's build: names only for the ASCII check, which decimal ids pass
+  uint64_t last_n_segs = 0;   // S lines of the last build (paths = records - edges - S lines)
   hipStream_t stream = nullptr;
   hipStream_t side = nullptr;   // work that overlaps the main stream (the decimal names blob)
   hipEvent_t side_ev[2] = {nullptr, nullptr};  // main -> side fork, side -> main join
@@ -1667,6 +1672,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   R->n_lines = (int64_t)n_lines;
   R->n_edges = (int64_t)n_e;
   R->n_records = (int64_t)tot.recs;
+  c->last_n_segs = n_s;
   if (n_t >= 0xFFFFFFFFull || n_e >= 0xFFFFFFFFull)
     throw Failure(G2N_E_UNSUPPORTED, "more than 2^32-1 node touches in one build");
   if (!local_done) phase(c, "tiles");
@@ -1885,8 +1891,8 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
     R->names_blob = blob;
     R->names_offsets = offs;
     phase(c, "names");
-  } else if (o->want_node_names && lean_done && c->edge_text && !name_pre_len) {
-    c->names_dec = true;  // k_edge_dec_text renders them from the ids
+  } else if (o->want_node_names && lean_done && (c->edge_text || c->stats_names) && !name_pre_len) {
+    c->names_dec = true;  // k_edge_dec_text renders them from the ids; the stats' ASCII check needs none
   } else if (o->want_node_names && lean_done) {
     auto* offs = dget<int64_t>(c, S_OFFS, n_nodes + 1);
     const uint64_t names_len = dec_name_off(n_nodes, (int)bidir) + (uint64_t)name_pre_len * n_nodes;
@@ -2257,6 +2263,164 @@ static void download_result(g2n_context* c, const g2n_result& D, HostResult* H) 
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
+// --------------------------------------------------------- graph statistics ------
+// g2n_csr_stats on c's stream (the caller holds c's lock and opened the call).
+template <class I>
+static void csr_stats_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz, bool directed,
+                        StatsOut* so, hipEvent_t* ev) {
+  auto* parent = dget<uint32_t>(c, S_STPARENT, n);
+  auto* diag = dget<uint8_t>(c, S_STDIAG, n);
+  uint32_t* colcnt = directed ? dget<uint32_t>(c, S_STCOL, n) : nullptr;
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_STLONG, long_cap);
+  const unsigned g = grid_for(n);
+  const unsigned gr = (unsigned)std::min<uint64_t>(g, (uint64_t)c->n_cu * 8);
+  // ---- degrees (this walk also queues the long rows for both walks)
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  G2N_HIP(hipMemsetAsync(diag, 0, n, c->stream));
+  if (colcnt) G2N_HIP(hipMemsetAsync(colcnt, 0, n * sizeof(uint32_t), c->stream));
+  const DegOp dop{diag, colcnt};
+  hipLaunchKernelGGL((k_rows_short<I, DegOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, dop, 1,
+                     long_rows, long_cap, so);
+  hipLaunchKernelGGL((k_rows_long<I, DegOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, dop,
+                     (const uint32_t*)long_rows, long_cap, so);
+  hipLaunchKernelGGL(k_deg_max<I>, dim3(gr), dim3(256), 0, c->stream, indptr, n, nnz, (const uint8_t*)diag,
+                     (const uint32_t*)colcnt, so);
+  G2N_HIP(hipEventRecord(ev[1], c->stream));
+  // ---- components
+  const HookOp hop{parent};
+  hipLaunchKernelGGL(k_cc_init<I>, dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, parent, so);
+  hipLaunchKernelGGL((k_rows_short<I, HookOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop, 0,
+                     long_rows, long_cap, so);
+  hipLaunchKernelGGL((k_rows_long<I, HookOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop,
+                     (const uint32_t*)long_rows, long_cap, so);
+  hipLaunchKernelGGL(k_cc_flatten, dim3(gr), dim3(256), 0, c->stream, parent, n, so);
+  G2N_HIP(hipEventRecord(ev[2], c->stream));
+}
+
+static StatsOut* stats_out_reset(g2n_context* c) {
+  auto* so = dget<StatsOut>(c, S_STOUT, 1);
+  G2N_HIP(hipMemsetAsync(so, 0, sizeof(StatsOut), c->stream));
+  G2N_HIP(hipMemsetAsync(&so->high_off, 0xFF, sizeof(so->high_off), c->stream));
+  return so;
+}
+
+static void csr_stats(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
+                      uint64_t nnz, int32_t directed, g2n_graph_stats* out) {
+  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, "g2n_csr_stats: index_width must be 4 or 8");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats: 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats: 2^32-1 or more entries");
+  std::memset(out, 0, sizeof(*out));
+  out->n_nodes = (int64_t)n;
+  out->n_entries = (int64_t)nnz;
+  if (n == 0) {
+    if (nnz) throw Failure(G2N_E_ARG, "g2n_csr_stats: entries without rows");
+    return;
+  }
+  if (!indptr || (nnz && !indices)) throw Failure(G2N_E_ARG, "g2n_csr_stats: null array");
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (auto& x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
+  StatsOut* so = stats_out_reset(c);
+  if (index_width == 4)
+    csr_stats_t<int32_t>(c, (const int32_t*)indptr, (const int32_t*)indices, n, nnz, directed != 0, so, ev.e);
+  else
+    csr_stats_t<int64_t>(c, (const int64_t*)indptr, (const int64_t*)indices, n, nnz, directed != 0, so, ev.e);
+  const StatsOut h = read_dev(c, so);
+  if (h.bad) throw Failure(G2N_E_ARG, "g2n_csr_stats: indptr / indices out of range");
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  out->ms_degree = ms;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+  out->ms_components = ms;
+  out->n_diag = (int64_t)h.n_diag;
+  out->n_components = (int64_t)h.n_roots;
+  out->max_degree = (int64_t)h.max_degree;
+}
+
+int csr_stats_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                   int32_t directed, int32_t device, g2n_graph_stats* out) {
+  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, "g2n_csr_stats_host: index_width must be 4 or 8");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats_host: 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats_host: 2^32-1 or more entries");
+  if (!indptr || (nnz && !indices)) throw Failure(G2N_E_ARG, "g2n_csr_stats_host: null array");
+  g2n_context* c = shared_context(device);
+  std::lock_guard<std::mutex> lk(c->mu);
+  enter_call(c);
+  G2N_HIP(hipSetDevice(c->device));
+  clear_call_state(c);
+  const size_t w = (size_t)index_width;
+  void* dip = dbuf(c, S_STIP, (size_t)(n + 1) * w);
+  void* dix = dbuf(c, S_STIX, (size_t)nnz * w);
+  G2N_HIP(hipMemcpyAsync(dip, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
+  if (nnz) G2N_HIP(hipMemcpyAsync(dix, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
+  csr_stats(c, dip, dix, index_width, n, nnz, directed, out);
+  shrink_shared(c);
+  return G2N_OK;
+}
+
+static thread_local const StatsRequest* t_stats_request = nullptr;
+void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
+
+// A stats build's result (g2n_stats_from_path): D's CSR stays on the device, the statistics are
+// taken from it there, and H receives D's scalars — plus the one key the ASCII check objects to.
+static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, const StatsRequest& q) {
+  g2n_result& R = H->r;
+  std::memcpy(&R, &D, sizeof(g2n_result));
+  R.priv_ = H;
+  R.err_detail = nullptr;
+  R.names_blob = nullptr;
+  R.names_offsets = nullptr;
+  R.names_bytes = 0;
+  R.rows = R.cols = R.indptr = R.indices = R.data = nullptr;
+  if (D.err_detail) R.err_detail = (const uint8_t*)download(c, H->detail, D.err_detail, (size_t)D.err_detail_len);
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  if (D.status != G2N_OK) return;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_stats_from_path: the build returned no CSR");
+  csr_stats(c, D.indptr, D.indices, D.index_width, (uint64_t)D.n_nodes, (uint64_t)D.nnz, q.directed, q.out);
+  *q.n_paths = D.n_records - D.n_edges - (int64_t)c->last_n_segs;
+  if (!q.check_ascii || !D.names_blob || !D.names_bytes || !D.n_nodes) return;
+  StatsOut* so = stats_out_reset(c);
+  const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
+  hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
+  hipLaunchKernelGGL(k_high_owner, dim3(1), dim3(64), 0, c->stream, D.names_offsets, (uint64_t)D.n_nodes, so);
+  const StatsOut h = read_dev(c, so);
+  if (h.high_off == ~0ull) return;
+  if (h.high_id < 0 || h.high_id >= D.n_nodes) throw Failure(G2N_E_DEVICE, "g2n_stats_from_path: key lookup failed");
+  int64_t span[2];
+  G2N_HIP(hipMemcpyAsync(span, D.names_offsets + h.high_id, sizeof(span), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  R.err_detail = (const uint8_t*)download(c, H->detail, D.names_blob + span[0], (size_t)(span[1] - span[0]));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  R.err_detail_len = span[1] - span[0];
+  R.status = G2N_E_UNICODE;
+  R.err_line = -1;
+  R.err_index = h.high_id;
+  set_last_error("a node key is not ASCII (the graph path decodes node keys as ASCII)");
+}
+
+// the outputs of one host build: the matrix and names, or (a stats request) the statistics' scalars
+static void host_result(g2n_context* c, const g2n_result& D, HostResult* H) {
+  if (t_stats_request)
+    stats_result(c, D, H, *t_stats_request);
+  else
+    download_result(c, D, H);
+}
+
+static int run_host_pipeline(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, g2n_result* R) {
+  struct Flag {
+    g2n_context* c;
+    ~Flag() { c->stats_names = false; }
+  } flag{c};
+  c->stats_names = t_stats_request != nullptr;
+  return run_pipeline(c, in, len, o, R);
+}
+
 int build_host_fill(size_t len, const FillFn& fill, const g2n_options* opts, g2n_result** out, double read_ms) {
   g2n_context* c = shared_context(opts->device);
   std::lock_guard<std::mutex> lk(c->mu);
@@ -2268,11 +2432,11 @@ int build_host_fill(size_t len, const FillFn& fill, const g2n_options* opts, g2n
   staged_upload(c->device, din, len, fill);
   double t1 = now_ms();
   g2n_result D;
-  run_pipeline(c, din, len, opts, &D);
+  run_host_pipeline(c, din, len, opts, &D);
   double t2 = now_ms();
   HostResult* H = new_host_result();
   try {
-    download_result(c, D, H);
+    host_result(c, D, H);
   } catch (...) {
     delete H;
     throw;
@@ -2315,11 +2479,11 @@ int build_host_bgzf(const uint8_t* z, size_t zlen, const std::vector<ZMember>& m
   if (n_bad) return kBgzfFallback;
   const double t1 = now_ms();
   g2n_result D;
-  run_pipeline(c, din, total_out, opts, &D);
+  run_host_pipeline(c, din, total_out, opts, &D);
   const double t2 = now_ms();
   HostResult* H = new_host_result();
   try {
-    download_result(c, D, H);
+    host_result(c, D, H);
   } catch (...) {
     delete H;
     throw;
@@ -3134,6 +3298,20 @@ int g2n_count_device(g2n_context* ctx, const void* d_input, size_t len, int64_t*
     out4[3] = (int64_t)tot.recs;
   });
   return G2N_OK;
+}
+
+int g2n_csr_stats(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width, uint64_t n,
+                  uint64_t nnz, int32_t directed, g2n_graph_stats* out) {
+  if (!out) return G2N_E_ARG;
+  G2N_CTX_CALL(ctx, g2n::csr_stats(ctx, d_indptr, d_indices, index_width, n, nnz, directed, out));
+  return G2N_OK;
+}
+
+int g2n_csr_stats_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                       int32_t directed, int32_t device, g2n_graph_stats* out) {
+  if (!out) return G2N_E_ARG;
+  return g2n::guarded(
+      [&] { return g2n::csr_stats_host(indptr, indices, index_width, n, nnz, directed, device, out); });
 }
 
 int g2n_device_memory(int32_t device, uint64_t* free_bytes, uint64_t* total_bytes) {

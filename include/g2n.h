@@ -456,6 +456,45 @@ int g2n_count_device(g2n_context *ctx, const void *d_input, size_t len, int64_t 
 int g2n_build_decimal_range(g2n_context *ctx, const void *d_input, size_t len, const g2n_options *opts,
                             int64_t *ev6, g2n_result *out);
 
+/* ---- graph statistics (gfa2network/analysis.py:33-65 compute_stats, cli.py:364-376) ------------
+ * What the reference reads off a NetworkX graph, as integer work on a CSR's structure (the values
+ * are never read): n_nodes = n, n_entries = nnz, n_diag = rows that hold their own index,
+ * n_components = connected components with every stored (u, v) joining u and v (isolated nodes
+ * count; a lock-free union-find, the same count on every run), max_degree = the largest of
+ *   directed (nx.DiGraph):  row length + occurrences of the row's index as a column
+ *   undirected (nx.Graph):  row length + 1 if the row holds its own index
+ * (0 when n == 0).  Edges and density follow from these in the caller (Python ints: n * (n - 1)
+ * passes 2^53 inside the supported range).  ms_*: hipEvent times of the two kernel groups. */
+typedef struct g2n_graph_stats {
+  int64_t n_nodes, n_entries, n_diag, n_components, max_degree;
+  double ms_degree, ms_components; /* hipEvent, pipeline stream */
+} g2n_graph_stats;
+
+/* d_indptr (n + 1) / d_indices (nnz): DEVICE pointers on ctx's device, index_width 4 (int32) or 8
+ * (int64) bytes per element; scratch from ctx's arena; returns after the stream drained.
+ * G2N_E_UNSUPPORTED for n >= 2^31 - 1 or nnz >= 2^32 - 1 (the build's own limits); G2N_E_ARG when
+ * indptr is not a non-decreasing map into [0, nnz] or an index is outside [0, n) (nothing out of
+ * range is ever addressed). */
+int g2n_csr_stats(g2n_context *ctx, const void *d_indptr, const void *d_indices, int32_t index_width, uint64_t n,
+                  uint64_t nnz, int32_t directed, g2n_graph_stats *out);
+
+/* The same for a CSR in HOST memory: uploaded to `device` (the host entry points' cached context). */
+int g2n_csr_stats_host(const void *indptr, const void *indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                       int32_t directed, int32_t device, g2n_graph_stats *out);
+
+/* compute_stats(path): the input is ingested as by g2n_build_from_path (plain, gzip, BGZF) and
+ * built as a plain graph — of opts only directed, strip_orientation, want_node_names, device,
+ * unknown_warned and test_flags are read; the build is not bidirected, unweighted, asymmetric, its
+ * output the summed CSR, which stays on the device — then g2n_csr_stats runs on it and only the
+ * scalars come back.  *n_paths = the P / O records (records - edges - S lines).  *res (free with
+ * g2n_result_free) carries status, error and warning fields, counts and phase times as a build's,
+ * no matrix and no names.  want_node_names = 1 asks for the graph path's ASCII decode of node keys
+ * (builders.py:155-162; 0 = raw_bytes_id): after a clean build, a key with a byte >= 0x80 gives
+ * status G2N_E_UNICODE with err_line = -1, err_index = the lowest such node id and err_detail = its
+ * key (whose .decode("ascii") raises the reference's error). */
+int g2n_stats_from_path(const char *path, const g2n_options *opts, g2n_graph_stats *out, int64_t *n_paths,
+                        g2n_result **res);
+
 #ifdef __cplusplus
 }
 #endif
