@@ -495,6 +495,8 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
   auto* off1 = dget<uint32_t>(c, S_POFF, (words ? 2 : 1) * nm1);
   auto* el1 = dget<uint2>(c, S_EL0, n_el);
   uint32_t* wa1 = words ? dget<uint32_t>(c, S_PW0, n_trip) : nullptr;
+  // the last pass's words are what F1 reads: 16 bits wide (pass 1 / 4 when it is the only pass, else pass 7)
+  src.w16 = bits2 == 0 ? 1u : 0u;
   if (sum && !t_rows) {  // the SUM CSR: one element per entry, adjacent transposed twins as one (a word)
     src.pair_bits = (uint32_t)low + 1u;
     hipLaunchKernelGGL(k_part_hist<4>, dim3((unsigned)n_blk1), dim3(kPartTPB), 0, c->stream, src, shift1, n_dig1,
@@ -518,7 +520,7 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
   auto* bst = dget<uint32_t>(c, S_BSTART, n_buckets + 1);
   uint32_t* bstA = words ? dget<uint32_t>(c, S_BSTARTA, n_buckets + 1) : nullptr;
   const uint2* el = el1;
-  const uint32_t* wa = wa1;
+  const uint16_t* wa = (const uint16_t*)wa1;
   if (bits2 == 0) {
     hipLaunchKernelGGL(k_part_bucket_starts1, dim3(grid_for(n_buckets + 1)), dim3(kTPB), 0, c->stream,
                        (const uint32_t*)off1, (const uint32_t*)cnt1, n_blk1, n_buckets, bst, (const uint32_t*)nullptr);
@@ -546,7 +548,7 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
     PartSrc s2a{nullptr, nullptr, 0, 0, nullptr, nullptr, 0, 0, nullptr, grpA, grpA + n_dig1 + 1, n_dig1,
                 nullptr, 0, (uint32_t)low + 1u, nullptr, wa1, ptile};
     s2a.obase = off2 + n2;
-    uint32_t* wa2 = words ? dget<uint32_t>(c, S_PW1, n_trip) : nullptr;
+    uint16_t* wa2 = words ? dget<uint16_t>(c, S_PW1, n_trip) : nullptr;  // (u16 words out)
     const bool wide = bits2 > (int)kMaxDigitBits;
     if (wide) {
       hipLaunchKernelGGL((k_part_hist<2, kWideDigitBits>), dim3((unsigned)n_blk2), dim3(kPartTPB), 0, c->stream, s2,
@@ -575,10 +577,11 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
       if (wide)
         hipLaunchKernelGGL((k_part_scatter<7, kWideDigitBits>), dim3((unsigned)n_blk2), dim3(kPartTPB), 0,
                            c->stream, s2a, 2u * (uint32_t)low, n_dig2, (const uint32_t*)(off2 + n2), n_blk2,
-                           (uint2*)nullptr, wa2);
+                           (uint2*)nullptr, (uint32_t*)wa2);
       else
         hipLaunchKernelGGL(k_part_scatter<7>, dim3((unsigned)n_blk2), dim3(kPartTPB), 0, c->stream, s2a,
-                           2u * (uint32_t)low, n_dig2, (const uint32_t*)(off2 + n2), n_blk2, (uint2*)nullptr, wa2);
+                           2u * (uint32_t)low, n_dig2, (const uint32_t*)(off2 + n2), n_blk2, (uint2*)nullptr,
+                           (uint32_t*)wa2);
       hipLaunchKernelGGL(k_part_bucket_starts, dim3(grid_for(n_buckets + 1)), dim3(kTPB), 0, c->stream,
                          (const uint32_t*)(off2 + n2), s2a, n_dig2, n_buckets, bstA);
       wa = wa2;
@@ -645,6 +648,10 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
     int32_t nnz = 0;  // one wait for the overflow flag and the entry count
     G2N_HIP(hipMemcpyAsync(&nnz, indptr + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     sync_ctl(c);
+#ifdef G2N_F1_STAMPS
+    // (stamps are indexed by block: every range wrote the same slots, the last range's remain)
+    stamps_to_file(c, "G2N_F1_STAMPS_OUT", f1st, n_bk / n_ov * kF1Stamps);
+#endif
     if (c->h_ctl->bucket_overflow) return false;
     R->format = G2N_FMT_CSR;
     R->indptr = indptr;

@@ -32,6 +32,7 @@
 
 #include "g2n_kernels.h"
 #include "g2n_scan.hip"
+#include "g2n_symword.h"
 
 namespace g2n {
 
@@ -45,6 +46,8 @@ constexpr uint32_t kWideDigitBits = 11;            // pass 2 of a partition past
 // (F1 is compiled for 8 waves per SIMD: its 106 SGPRs held it to 7; capped, 34 of them spill to VGPR
 // lanes and the VGPRs stay at 62)
 constexpr uint32_t kFinTPB = 256;                  // threads (= rows) of a finish block
+// (the last pass's pair words are u16: two rows of a bucket, low <= kSymLowMax = 8 bits each)
+static_assert(kFinTPB == 1u << kSymLowMax, "a finish bucket's row must fit the 8-bit fields of a 16-bit pair word");
 constexpr uint32_t kSymCap = 16 * kFinTPB;         // elements one finish block holds
 constexpr uint32_t kSymPer = kSymCap / kFinTPB;    // 16 per thread
 constexpr uint32_t kSymReg = 8;                    // stored elements per thread kept in registers
@@ -105,6 +108,8 @@ struct PartSrc {
   // a count matrix scanned together with the one before it (one scan launch for passes 2 and 7): the
   // device word holding that scan's value at this matrix's start, subtracted from every offset read
   const uint32_t* obase = nullptr;
+  // passes 1 / 4 as the only pass: the pair words go out 16 bits wide (F1 reads u16 words; 2 low <= 16)
+  uint32_t w16 = 0;
 };
 
 // Passes 5 / 6: passes 4 / 2 of the weighted SUM CSR (coo.tocsr of a weighted COO whose duplicate
@@ -119,8 +124,11 @@ constexpr bool kHasW = kPass == 5 || kPass == 6;
 // share the bucket, so the word holds a's bits below pass 1's digit and b's bits below `low`:
 // word = (a mod 2^shift1) << low | (b mod 2^low) (shift1 + low <= 26 bits).  Pass 7 is pass 2 over
 // stream A (words in, words out; digit = word >> 2 low = bits of a >> low); F1 rebuilds (a, b) from the
-// bucket id.
-// Half the bytes of those elements through the rest of the partition and into F1.
+// bucket id (sym_word_rows, g2n_symword.h).
+// Half the bytes of those elements through the rest of the partition and into F1.  The last pass
+// writes its words 16 bits wide (pass 7, or pass 1 / 4 as the only pass: PartSrc::w16): below the
+// spent digit a word is 2 low <= 16 bits, and F1 loads u16 words — half of pass 7's payload and of
+// F1's word reads again (C4: pass 7 0.63 -> 0.53 ms).
 template <int kPass>
 constexpr bool kSplit = kPass == 1 || kPass == 4;  // MAX-SYM pass 1, and the SUM CSR's twins (pass 4)
 template <int kPass>
@@ -413,12 +421,14 @@ __global__ void __launch_bounds__(kPartTPB)
       if constexpr (kSplit<kPass>) {
         if ((y.y & 3u) == kElPair) {  // stream A: the pair word
           d += n_dig;
-          wout[cur[d] + (i - hist[d])] = pair_word(y, shift, low, S.row_base);
+          const uint32_t w = pair_word(y, shift, low, S.row_base);
+          if (S.w16) ((uint16_t*)wout)[cur[d] + (i - hist[d])] = (uint16_t)w;  // (block-uniform)
+          else wout[cur[d] + (i - hist[d])] = w;
           continue;
         }
       }
-      if constexpr (kWords<kPass>) {
-        wout[cur[d] + (i - hist[d])] = y.x;
+      if constexpr (kWords<kPass>) {  // the last pass: the digit's bits (from 2 low up) are spent
+        ((uint16_t*)wout)[cur[d] + (i - hist[d])] = (uint16_t)y.x;
       } else {
         out[cur[d] + (i - hist[d])] = y;
         if constexpr (kHasW<kPass>) wout[cur[d] + (i - hist[d])] = wstage[i];
@@ -612,7 +622,7 @@ template <class T, bool kSum>
 __global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8, 8))) k_sym_finish(const uint2* __restrict__ el, const uint32_t* __restrict__ bstart,
                                                      uint32_t low, uint64_t n_rows, T one, uint32_t* __restrict__ btot,
                                                      uint32_t* __restrict__ tcol, uint16_t* __restrict__ tcn,
-                                                     int32_t* __restrict__ indptr, Ctl* ctl, uint32_t row_base, const uint32_t* __restrict__ wa,
+                                                     int32_t* __restrict__ indptr, Ctl* ctl, uint32_t row_base, const uint16_t* __restrict__ wa,
                                                      const uint32_t* __restrict__ bstA, uint32_t b0) {
   __shared__ __attribute__((aligned(16))) uint32_t seg[kSymCap];  // values (column << 1 | side) grouped by row; then merged columns
   __shared__ uint32_t cnt[kFinTPB];
@@ -648,9 +658,10 @@ __global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8,
     // a bucket of more stored elements (rare: a skewed bucket) reads the rest again, so F1 keeps
     // to 64 VGPRs — 4 blocks per CU
     // the registers hold stream A's words (most of a bucket) or, without stream A, B's elements
-    const uint32_t hi = (uint32_t)b << low;  // a pair word's row bits above low
-    auto word = [&](uint32_t w) {
-      return make_uint2(hi | ((w >> low) & rmask), (((hi | (w & rmask)) + row_base) << 2) | kElPair);
+    auto word = [&](uint32_t w) {  // (the bucket id gives a pair word's row bits above low)
+      uint32_t ra, rb;
+      sym_word_rows(w, (uint32_t)b, low, &ra, &rb);
+      return make_uint2(ra, ((rb + row_base) << 2) | kElPair);
     };
     const uint32_t nr = bstA ? nA : nB;
     uint2 xs[kSymReg];
