@@ -41,6 +41,8 @@ EXPORTED = [
     "g2n_keyset_create", "g2n_keyset_add", "g2n_keyset_view", "g2n_keyset_free",
     "g2n_gunzip", "g2n_gunzip_chunked", "g2n_free", "g2n_split_render", "g2n_split_get", "g2n_split_segments", "g2n_split_free", "g2n_join_names", "g2n_gather_names", "g2n_write_npz", "g2n_write_node_map", "g2n_first_bad_utf8",
     "g2n_csr_stats", "g2n_csr_stats_host", "g2n_stats_from_path",
+    "g2n_csr_path_distances", "g2n_csr_path_distances_host", "g2n_load_paths", "g2n_paths_get", "g2n_paths_free",
+    "g2n_distances_from_path",
 ]
 
 
@@ -147,6 +149,20 @@ class GraphStats(ctypes.Structure):
         ("ms_components", ctypes.c_double),
     ]
 
+
+class DistInfo(ctypes.Structure):
+    """g2n_dist_info (include/g2n.h)."""
+
+    _fields_ = [
+        ("levels", ctypes.c_int64),
+        ("launches", ctypes.c_int64),
+        ("batches", ctypes.c_int64),
+        ("ms_resolve", ctypes.c_double),
+        ("ms_bfs", ctypes.c_double),
+    ]
+
+
+DIST_MIN, DIST_MEAN = 0, 1
 
 _lib = None
 
@@ -310,6 +326,20 @@ def load() -> ctypes.CDLL:
     lib.g2n_stats_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), ctypes.POINTER(GraphStats),
                                         ctypes.POINTER(I64), ctypes.POINTER(ctypes.POINTER(Result))]
     lib.g2n_stats_from_path.restype = ctypes.c_int
+    lib.g2n_csr_path_distances.argtypes = [P, P, P, I32, U64, U64, P, P, U64, I32, P, ctypes.POINTER(DistInfo)]
+    lib.g2n_csr_path_distances.restype = ctypes.c_int
+    lib.g2n_csr_path_distances_host.argtypes = [P, P, I32, U64, U64, P, P, U64, I32, P, I32, ctypes.POINTER(DistInfo)]
+    lib.g2n_csr_path_distances_host.restype = ctypes.c_int
+    lib.g2n_load_paths.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
+    lib.g2n_load_paths.restype = ctypes.c_int
+    lib.g2n_paths_get.argtypes = [P] + [P] * 9
+    lib.g2n_paths_get.restype = None
+    lib.g2n_paths_free.argtypes = [P]
+    lib.g2n_paths_free.restype = None
+    lib.g2n_distances_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), P, I64, I64, I32, P,
+                                            ctypes.POINTER(DistInfo), ctypes.POINTER(I32), ctypes.POINTER(I64),
+                                            ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_distances_from_path.restype = ctypes.c_int
     for f in ("g2n_keyset_create", "g2n_keyset_add", "g2n_keyset_view", "g2n_partition_keys", "g2n_dedup_keys", "g2n_gather_keys", "g2n_remap_pairs", "g2n_route_triplets", "g2n_csr_from_coo_pair",
               "g2n_context_group_slots", "g2n_route_group_slots", "g2n_csr_from_group_slots",
               "g2n_upload_file_range", "g2n_count_device", "g2n_build_decimal_range", "g2n_order_keys",
@@ -504,7 +534,111 @@ def csr_stats_host(indptr: np.ndarray, indices: np.ndarray, n: int, directed: bo
     return _stats_dict(st)
 
 
-BAND_ENTRIES = 2**31 - 2  # entries one g2n_coo_to_csr_band call takes (the weighted row-sum path's limit)
+def csr_path_distances_host(indptr: np.ndarray, indices: np.ndarray, n: int, path_ptr: np.ndarray,
+                            path_nodes: np.ndarray, mean: bool, device: int = 0) -> tuple[tuple, dict]:
+    """g2n_csr_path_distances_host on a host CSR's structure (indptr / indices both int32 or both
+    int64) and K paths (int64 path_ptr of K + 1 offsets, int64 path_nodes): ((D,) or (S, C), the
+    g2n_dist_info fields) — the directed K x K tables, uint32 D (0xFFFFFFFF = unreached) or uint64
+    S and C."""
+    lib = load()
+    idt = np.dtype(indptr.dtype)
+    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
+        raise TypeError("indptr / indices must both be int32 or both int64")
+    ip, ix = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
+    pp = np.ascontiguousarray(path_ptr, dtype=np.int64)
+    pn = np.ascontiguousarray(path_nodes, dtype=np.int64)
+    if len(ip) != n + 1:
+        raise ValueError("indptr must hold n + 1 offsets")
+    K = len(pp) - 1
+    if K < 0 or pp[0] != 0 or pp[K] != len(pn):
+        raise ValueError("path_ptr must hold K + 1 offsets from 0 to len(path_nodes)")
+    out = np.empty((2, K, K), dtype=np.uint64) if mean else np.empty((1, K, K), dtype=np.uint32)
+    info = DistInfo()
+    rc = lib.g2n_csr_path_distances_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, n, len(ix),
+                                         pp.ctypes.data, pn.ctypes.data if pn.size else None, K,
+                                         DIST_MEAN if mean else DIST_MIN, out.ctypes.data if out.size else None,
+                                         int(device), ctypes.byref(info))
+    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
+        raise NotImplementedError(f"GPU path distances: {last_error()}")
+    if rc == E_ARG:
+        raise ValueError(f"GPU path distances: {last_error()}")
+    if rc != OK:
+        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+    return tuple(out), {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
+                        "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
+
+
+class Paths:
+    """g2n_load_paths' result (freed with the object): ``names`` / ``name_offs`` (K + 1), ``steps`` /
+    ``step_offs``, ``path_ptr`` (K + 1 offsets into the steps) as numpy copies, ``bad_line`` (-1:
+    none) and ``bad_bytes`` — the first P / O name or step that is not ASCII."""
+
+    def __init__(self, path: str):
+        lib = load()
+        self._lib, self._h = lib, ctypes.c_void_p()
+        rc = lib.g2n_load_paths(os.fsencode(path), ctypes.byref(self._h))
+        self.status = rc
+        if rc != OK:
+            self._h = ctypes.c_void_p()
+            self.message = last_error()
+            self.n_paths, self.bad_line, self.bad_bytes = 0, -1, b""
+            return
+        P8, P64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)
+        names, steps, bad = P8(), P8(), P8()
+        noffs, soffs, pptr = P64(), P64(), P64()
+        k, bad_len, bad_line = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int64(-1)
+        lib.g2n_paths_get(self._h, ctypes.byref(names), ctypes.byref(noffs), ctypes.byref(k), ctypes.byref(steps),
+                          ctypes.byref(soffs), ctypes.byref(pptr), ctypes.byref(bad_line), ctypes.byref(bad),
+                          ctypes.byref(bad_len))
+        self.n_paths = K = int(k.value)
+
+        def arr(ptr, n, dt):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        self.name_offs = arr(noffs, K + 1, np.int64)
+        self.path_ptr = arr(pptr, K + 1, np.int64)
+        self.step_offs = arr(soffs, int(self.path_ptr[K]) + 1, np.int64)
+        self.names = arr(names, int(self.name_offs[K]), np.uint8)
+        self.steps = arr(steps, int(self.step_offs[-1]), np.uint8)
+        self.bad_line = int(bad_line.value)
+        self.bad_bytes = bytes(arr(bad, int(bad_len.value), np.uint8)) if self.bad_line >= 0 else b""
+
+    def name(self, k: int) -> bytes:
+        return bytes(self.names[self.name_offs[k]:self.name_offs[k + 1]])
+
+    def step(self, s: int) -> bytes:
+        return bytes(self.steps[self.step_offs[s]:self.step_offs[s + 1]])
+
+    def as_dict(self) -> dict:
+        """name -> list of steps, as bytes, in the reference's order."""
+        sb = bytes(self.steps)
+        so, pp = self.step_offs.tolist(), self.path_ptr.tolist()
+        return {self.name(k): [sb[so[s]:so[s + 1]] for s in range(pp[k], pp[k + 1])] for k in range(self.n_paths)}
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.g2n_paths_free(self._h)
+            self._h = None
+
+
+def distances_from_path(path: str, opts: Options, paths: Paths, source: int, target: int, mean: bool):
+    """g2n_distances_from_path: (the build's result without a matrix, the tables — (D,) or (S, C), K x K
+    for source < 0 else 2 x 2 —, the g2n_dist_info fields, the orientation flag, the first missing
+    step or -1).  The tables are meaningful only when the status is OK and no step is missing."""
+    lib = load()
+    K = paths.n_paths if source < 0 else 2
+    out = np.zeros((2, K, K), dtype=np.uint64) if mean else np.full((1, K, K), 0xFFFFFFFF, dtype=np.uint32)
+    info, oriented, missing = DistInfo(), ctypes.c_int32(0), ctypes.c_int64(-1)
+    res = ctypes.POINTER(Result)()
+    rc = lib.g2n_distances_from_path(os.fsencode(path), ctypes.byref(opts), paths._h, source, target,
+                                     DIST_MEAN if mean else DIST_MIN, out.ctypes.data, ctypes.byref(info),
+                                     ctypes.byref(oriented), ctypes.byref(missing), ctypes.byref(res))
+    d = {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
+         "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
+    return _from_result(res, rc), tuple(out), d, bool(oriented.value), int(missing.value)
+
+
+BAND_ENTRIES = 2**31 - 2 # entries one g2n_coo_to_csr_band call takes (the weighted row-sum path's limit)
 
 
 def coo_to_csr(rows: np.ndarray, cols: np.ndarray, data: np.ndarray, n_rows: int, n_cols: int,

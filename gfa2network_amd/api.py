@@ -39,7 +39,8 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "compute_stats", "graph_stats", "density"]
+           "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "load_paths", "genome_distance", "genome_distance_matrix",
+           "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
 # build's device working set is at most about this many bytes per input byte (the lean decimal-id
@@ -773,18 +774,75 @@ def graph_stats(A, *, directed: bool = True, device: int = 0) -> dict:
             "max_degree": st["max_degree"], "density": density(st["n_nodes"], edges, directed)}
 
 
-def _stats_one_piece(path, device: int) -> None:
-    """compute_stats builds the file in one piece on one GPU: an input parse_gfa would build in
-    chunks (its working set past the GPU's free HBM) is outside it."""
+def min_table(D: np.ndarray) -> np.ndarray:
+    """The directed float64 table of g2n_csr_path_distances' uint32 ``D``: ``M[i][j]`` = the fewest
+    hops from a step of path i to a step of path j, ``inf`` where none is reached (0xFFFFFFFF), 0.0
+    on the diagonal (genome_distance_matrix sets it without a search)."""
+    M = D.astype(np.float64)
+    M[D == np.uint32(0xFFFFFFFF)] = np.inf
+    np.fill_diagonal(M, 0.0)
+    return M
+
+
+def mean_table(S: np.ndarray, C: np.ndarray) -> np.ndarray:
+    """genome_distance_matrix's symmetric mean from g2n_csr_path_distances' directed uint64 sums
+    ``S`` and counts ``C``: ``(S[i][j] + S[j][i]) / (C[i][j] + C[j][i])`` — one correctly rounded
+    division of two integers below 2^53 — ``inf`` where nothing is reached, 0.0 on the diagonal."""
+    num, den = S + S.T, C + C.T
+    if num.size and int(num.max()) >= 2**53:
+        raise NotImplementedError("a distance sum of 2^53 or more is not exact in float64")
+    M = np.full(S.shape, np.inf, dtype=np.float64)
+    np.divide(num.astype(np.float64), den.astype(np.float64), out=M, where=den > 0)
+    np.fill_diagonal(M, 0.0)
+    return M
+
+
+def path_distances(A, paths, *, method: str = "min", device: int = 0, return_info: bool = False):
+    """Hop distances between node lists over the graph whose adjacency structure is the square scipy
+    sparse matrix ``A`` (extension; the counterpart of ``graph_stats``): every stored (u, v) is an
+    edge u -> v of weight 1, the values are never read.  ``paths`` is a list of lists of node
+    indices, duplicates kept.  ``method="min"`` returns the directed K x K float64 table
+    (``M[i][j]`` = the fewest hops from path i to path j, ``inf`` when unreachable; the reference's
+    ``genome_distance_matrix`` holds ``M[i][j]`` for i < j in both triangles); any other value
+    returns its symmetric mean.  Runs on the GPU as a bit-parallel breadth-first search, 64 paths at
+    a time (g2n_csr_path_distances_host); a matrix in another format is converted first.
+    ``return_info=True`` also returns the g2n_dist_info fields (levels, launches, batches, ms_*)."""
+    if not sp.issparse(A):
+        raise TypeError("path_distances takes a scipy sparse matrix")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("path_distances takes a square matrix")
+    if A.format != "csr":
+        # structure only: unit values in a dtype whose sums cannot overflow
+        C = A.tocoo()
+        A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
+        A.sum_duplicates()
+    n = int(A.shape[0])
+    if n >= 2**31 - 1:
+        raise NotImplementedError("GPU path distances need node ids below 2^31 - 1")
+    lists = [np.asarray(p, dtype=np.int64).reshape(-1) for p in paths]
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in lists], out=ptr[1:])
+    nodes = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
+    mean = method != "min"
+    tabs, info = nat.csr_path_distances_host(np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt), n, ptr,
+                                             nodes, mean, device)
+    M = mean_table(*tabs) if mean else min_table(tabs[0])
+    return (M, info) if return_info else M
+
+
+def _stats_one_piece(path, device: int, who: str = "compute_stats", then: str = "graph_stats") -> None:
+    """compute_stats (and the path distances) build the file in one piece on one GPU: an input
+    parse_gfa would build in chunks (its working set past the GPU's free HBM) is outside them."""
     p = str(path)
     if not os.path.isfile(p):
         return  # the build raises the reference's OSError
     size = os.path.getsize(p)
     if _chunk_plan(_gz_inflated_estimate(p, size) if p.endswith(".gz") else size, device):
         raise NotImplementedError(
-            "compute_stats builds the graph in one piece on one GPU and this input's working set exceeds its free "
+            f"{who} builds the graph in one piece on one GPU and this input's working set exceeds its free "
             "HBM: build the matrix with parse_gfa(..., asymmetric=True) (chunked or sharded) and pass it to "
-            "graph_stats")
+            f"{then}")
 
 
 def compute_stats(path, *, directed: bool = True, strip_orientation: bool = False, raw_bytes_id: bool = False,
@@ -815,6 +873,204 @@ def compute_stats(path, *, directed: bool = True, strip_orientation: bool = Fals
     edges = _stats_edges(st, directed)
     return {"nodes": st["n_nodes"], "edges": edges, "paths": n_paths, "components": st["n_components"],
             "max_degree": st["max_degree"], "density": density(st["n_nodes"], edges, directed)}
+
+
+try:  # networkx is imported only for the exception types the reference's callers catch
+    from networkx import NetworkXNoPath, NodeNotFound
+except Exception:  # noqa: BLE001 - any import failure: the same names, the same messages
+    class NodeNotFound(KeyError):  # type: ignore[no-redef]
+        """A source step is not a node of the graph (networkx.NodeNotFound where networkx imports)."""
+
+        def __str__(self) -> str:
+            return str(self.args[0]) if self.args else ""
+
+    class NetworkXNoPath(Exception):  # type: ignore[no-redef]
+        """No step of the target is reached (networkx.NetworkXNoPath where networkx imports)."""
+
+_ORIENTED_WARNING = "distance functions ignore orientation; use G.to_undirected()"
+
+
+def _warn_unsupported(raw: RawResult, stacklevel: int) -> None:
+    warnings.warn(f"Skipping unsupported record: {chr(raw.warn_byte)}", RuntimeWarning, stacklevel=stacklevel)
+
+
+def _named_file(path, who: str) -> str:
+    if hasattr(path, "read") or str(path) == "-":
+        raise NotImplementedError(f"{who} reads a named file (the reference parses its input twice)")
+    return str(path)
+
+
+def _load_paths_pass(raw: RawResult, ps: "nat.Paths", raw_bytes: bool, path) -> None:
+    """What the reference's load_paths raises and warns on its own pass over the file, from the one
+    build's result: the parser's errors in file order, with the ASCII decode of the first non-ASCII
+    P / O name or step at its record's line (a parse error on the same line comes first: the
+    parser raises inside the record), the gzip error after the lines read before it, and the
+    unsupported-record warning when its line precedes the error."""
+    dt = np.dtype("float64")
+    parse_failed = nat.OK < raw.status < nat.E_CAST_OVERFLOW and raw.err_line >= 0
+    if not raw_bytes and ps.bad_line >= 0 and not (parse_failed and raw.err_line <= ps.bad_line) and \
+            raw.status not in (nat.E_IO, nat.E_ARG, nat.E_DEVICE, nat.E_NOMEM, nat.E_UNSUPPORTED):
+        if 0 <= raw.warn_line < ps.bad_line:
+            _warn_unsupported(raw, 4)
+        ps.bad_bytes.decode("ascii")
+        raise AssertionError("decode of the reported bytes unexpectedly succeeded")
+    if parse_failed or raw.status >= nat.E_ARG:
+        finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=raw_bytes, verbose=False, build_matrix=False,
+                 path=path)
+        raise_for_status(raw, dt, path)
+    if raw.has_warning:
+        _warn_unsupported(raw, 4)
+
+
+def _graph_pass(raw: RawResult, raw_bytes_id: bool, verbose: bool, path) -> None:
+    """The graph build's own pass after a clean load_paths: its warning, progress strings and the
+    ASCII decode of node keys (builders.py:155-162)."""
+    dt = np.dtype("float64")
+    if raw.status == nat.E_UNICODE and raw.err_line < 0:
+        if raw.has_warning:
+            _warn_unsupported(raw, 4)
+        bytes(raw.err_detail).decode("ascii")
+        raise AssertionError("decode of the reported key unexpectedly succeeded")
+    finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=raw_bytes_id, verbose=verbose, build_matrix=False,
+             path=path)
+    raise_for_status(raw, dt, path)
+
+
+def _warn_oriented(raw: RawResult, oriented: bool) -> None:
+    """_warn_directed_bidirected on a directed graph (analysis.py:19-30).  Raw byte keys are decoded
+    as UTF-8 one by one until an oriented one is found: when a key has a byte >= 0x80 the build
+    returned the names, and the same loop runs here (its decode raises the reference's error)."""
+    if raw.names_offsets is not None:
+        blob, offs = bytes(raw.names_blob), raw.names_offsets.tolist()
+        oriented = False
+        for i in range(len(offs) - 1):
+            key = blob[offs[i]:offs[i + 1]].decode()
+            if key.endswith(":+") or key.endswith(":-"):
+                oriented = True
+                break
+    if oriented:
+        warnings.warn(_ORIENTED_WARNING, RuntimeWarning, stacklevel=3)
+
+
+def _unreadable(path: str, device: int) -> None:
+    """load_paths could not read the file: the build's own read raises the reference's OSError."""
+    raw = nat.build_from_path(path, nat.make_options(device=device))
+    dt = np.dtype("float64")
+    finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=False, verbose=False, build_matrix=False, path=path)
+    raise_for_status(raw, dt, path)
+    raise RuntimeError(f"load_paths: cannot read {path}")
+
+
+def load_paths(path, *, raw_bytes: bool = False, device: int = 0) -> dict:
+    """``load_paths`` (gfa2network/analysis.py:164-177): the P / O records as ``{name: [step, ...]}``
+    in first-occurrence order, a repeated name taking its last record's steps; ``str`` decoded as
+    ASCII unless ``raw_bytes``.  The records are read natively on host threads (g2n_load_paths); the
+    parser's own errors and its warning come from one GPU parse of the file.  ``device`` is an
+    extension."""
+    p = _named_file(path, "load_paths")
+    ps = nat.Paths(p)
+    if ps.status != nat.OK:
+        _unreadable(p, device)
+    raw, _st, _n = nat.stats_from_path(p, nat.make_options(asymmetric=True, output=nat.OUT_CSR, want_node_names=False,
+                                                           device=device))
+    _load_paths_pass(raw, ps, raw_bytes, path)
+    d = ps.as_dict()
+    if raw_bytes:
+        return d
+    return {k.decode("ascii"): [s.decode("ascii") for s in v] for k, v in d.items()}
+
+
+def _dist_opts(directed: bool, raw_bytes_id: bool, device: int):
+    return nat.make_options(directed=directed, asymmetric=True, output=nat.OUT_CSR, want_node_names=not raw_bytes_id,
+                            device=device)
+
+
+def _missing_step(step: bytes, raw_bytes_id: bool):
+    node = step if raw_bytes_id else step.decode("ascii")
+    return NodeNotFound(f"Node {node} not found in graph")
+
+
+def genome_distance_matrix(gfa_path, method: str = "min", *, raw_bytes_id: bool = False, backend: str = "networkx",
+                           verbose: bool = False, device: int = 0, return_info: bool = False):
+    """GPU ``genome_distance_matrix`` (gfa2network/analysis.py:180-272): the pairwise hop distances
+    between the file's P / O paths over the directed graph ``parse_gfa(gfa_path, build_graph=True)``
+    builds — ``min``: the fewest hops from a step of path i to a step of path j (i < j, in both
+    triangles); any other ``method``: the mean over both paths' steps of the distance from the other
+    path — as a ``pandas.DataFrame`` labelled with the path names when pandas imports, else an
+    ``ndarray``; with the reference's exceptions and warnings in its order.  The file is parsed once:
+    the CSR and the node names stay in HBM, the step names are looked up there and one bit-parallel
+    breadth-first search serves 64 paths (g2n_dist.hip); only the K x K tables come back.
+    ``backend="igraph"``, stdin and file objects raise NotImplementedError.  ``device`` and
+    ``return_info`` (also return the g2n_dist_info fields) are extensions."""
+    if backend == "igraph":
+        raise NotImplementedError("backend='igraph' is outside the GPU path")
+    p = _named_file(gfa_path, "genome_distance_matrix")
+    _stats_one_piece(p, device, "genome_distance_matrix", "path_distances")
+    ps = nat.Paths(p)
+    if ps.status != nat.OK:
+        _unreadable(p, device)
+    mean = method != "min"
+    raw, tabs, info, oriented, missing = nat.distances_from_path(p, _dist_opts(True, raw_bytes_id, device), ps, -1, -1,
+                                                                 mean)
+    _load_paths_pass(raw, ps, raw_bytes_id, gfa_path)
+    names = [ps.name(k) if raw_bytes_id else ps.name(k).decode("ascii") for k in range(ps.n_paths)]
+    _graph_pass(raw, raw_bytes_id, verbose, gfa_path)
+    _warn_oriented(raw, oriented)
+    if missing >= 0:
+        raise _missing_step(ps.step(missing), raw_bytes_id)
+    if mean:
+        M = mean_table(*tabs)
+    else:
+        M = min_table(tabs[0])
+        iu = np.triu_indices(len(M), 1)
+        M.T[iu] = M[iu]
+    try:
+        import pandas as pd
+    except Exception:  # noqa: BLE001 - the same broad guard as the reference
+        pd = None
+    if pd is not None:
+        labels = [n.decode() if isinstance(n, bytes) else str(n) for n in names]
+        M = pd.DataFrame(M, index=labels, columns=labels)
+    return (M, info) if return_info else M
+
+
+def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id: bool = False,
+                    verbose: bool = False, device: int = 0):
+    """``gfa2network distance GFA --path A B`` as a function (cli.py:323-346): the fewest hops from
+    a step of path ``name_a`` to a step of path ``name_b`` (an int; the search runs from A only) over
+    the graph ``parse_gfa(path, build_graph=True, directed=...)`` builds.  KeyError(name) for an
+    unknown path name (raised before the graph is built, after load_paths' own errors),
+    NodeNotFound when a step of A is no node, NetworkXNoPath when no step of B is reached."""
+    p = _named_file(path, "genome_distance")
+    _stats_one_piece(p, device, "genome_distance", "path_distances")
+    ps = nat.Paths(p)
+    if ps.status != nat.OK:
+        _unreadable(p, device)
+    index = {ps.name(k): k for k in range(ps.n_paths)}
+
+    def find(name):
+        key = name if isinstance(name, bytes) else str(name).encode()
+        if not raw_bytes_id and max(key, default=0) >= 0x80:
+            return None  # (the ASCII-decoded names hold no such key)
+        return index.get(key)
+
+    a, b = find(name_a), find(name_b)
+    opts = _dist_opts(directed, raw_bytes_id, device)
+    if a is None or b is None:
+        raw, _st, _n = nat.stats_from_path(p, opts)
+        _load_paths_pass(raw, ps, raw_bytes_id, path)
+        raise KeyError(name_a if a is None else name_b)
+    raw, tabs, _info, oriented, missing = nat.distances_from_path(p, opts, ps, a, b, False)
+    _load_paths_pass(raw, ps, raw_bytes_id, path)
+    _graph_pass(raw, raw_bytes_id, verbose, path)
+    if directed:
+        _warn_oriented(raw, oriented)
+    if missing >= 0:
+        raise _missing_step(ps.step(int(ps.path_ptr[a]) + missing), raw_bytes_id)
+    d = int(tabs[0][0, 1])
+    if d == 0xFFFFFFFF:
+        raise NetworkXNoPath("no path between node sets")
+    return d
 
 
 def _run(path, opts) -> RawResult:

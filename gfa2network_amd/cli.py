@@ -5,8 +5,10 @@ gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backen
 ``convert_format``, ``save_matrix`` (dense guard -> SystemExit), then the
 ``<matrix>.nodes.tsv`` sidecar.  ``export --format edge-list`` (cli.py:264-281) renders its
 lines on the GPU from the same parse; ``stats`` (cli.py:152-159, 364-376) prints
-``compute_stats``'s six numbers, taken on the GPU from the CSR.  Graph outputs (``--graph``,
-export graphml / gexf / json) and distance / distance-matrix are outside the GPU GFA->CSR path.
+``compute_stats``'s six numbers, taken on the GPU from the CSR; ``distance --path`` and
+``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same CSR.
+Graph outputs (``--graph``, export graphml / gexf / json) and ``distance --seq`` (sequences stored
+on nodes) are outside the GPU GFA->CSR path.
 """
 from __future__ import annotations
 
@@ -15,7 +17,8 @@ import sys
 from pathlib import Path
 
 from . import __version__
-from .api import compute_stats, convert_format, export_edge_list, parse_gfa, parse_gfa_names, save_matrix, save_node_map_native
+from .api import (compute_stats, convert_format, export_edge_list, genome_distance, genome_distance_matrix, parse_gfa,
+                  parse_gfa_names, save_matrix, save_node_map_native)
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -63,9 +66,22 @@ def _parser() -> argparse.ArgumentParser:
     g2.add_argument("--directed", dest="directed", action="store_true", default=True)
     g2.add_argument("--undirected", dest="directed", action="store_false")
     p_stats.add_argument("--strip-orientation", action="store_true")
-    for name in ("distance", "distance-matrix"):
-        sp_ = sub.add_parser(name, help="(outside the GPU GFA->CSR path)")
-        sp_.add_argument("rest", nargs=argparse.REMAINDER)
+    p_dist = sub.add_parser("distance", help="Compute distances")  # cli.py:161-175
+    p_dist.add_argument("gfa", help="Input *.gfa* file")
+    g3 = p_dist.add_mutually_exclusive_group(required=True)
+    g3.add_argument("--seq", nargs=2, metavar=("SEQ_A", "SEQ_B"))
+    g3.add_argument("--path", nargs=2, metavar=("PATH_A", "PATH_B"))
+    g4 = p_dist.add_mutually_exclusive_group()
+    g4.add_argument("--directed", dest="directed", action="store_true", default=True)
+    g4.add_argument("--undirected", dest="directed", action="store_false")
+    p_dist.add_argument("--backend", choices=["networkx", "igraph"], default="networkx", help="Graph backend to use")
+    p_dist.add_argument("--verbose", action="store_true")
+    p_dm = sub.add_parser("distance-matrix", help="Pairwise distances between paths")  # cli.py:177-189
+    p_dm.add_argument("gfa", help="Input *.gfa* file")
+    p_dm.add_argument("-o", "--output", required=True, help="Write matrix to PATH (.csv|.npy|.npz)")
+    p_dm.add_argument("--method", choices=["min", "mean"], default="min")
+    p_dm.add_argument("--backend", choices=["networkx", "igraph"], default="networkx", help="Graph backend to use")
+    p_dm.add_argument("--verbose", action="store_true")
     return parser
 
 
@@ -88,6 +104,33 @@ def main(argv: list[str] | None = None) -> None:
         print("density\t", f"{stats['density']:.6g}")
         return
     if args.cmd == "stat":
+        return
+    if args.cmd == "distance":  # cli.py:307-346
+        if args.seq:
+            parser.error("distance --seq needs sequences stored on nodes, outside the GPU GFA->CSR path")
+        if args.backend == "igraph":
+            parser.error("--backend igraph is outside the GPU GFA->CSR path")
+        name_a, name_b = args.path
+        try:
+            dist = genome_distance(args.gfa, name_a.encode() if args.raw_bytes_id else name_a,
+                                   name_b.encode() if args.raw_bytes_id else name_b, directed=args.directed,
+                                   raw_bytes_id=args.raw_bytes_id, verbose=args.verbose, device=args.device)
+        except KeyError as exc:
+            if type(exc) is not KeyError:  # (a NodeNotFound defined without networkx)
+                raise
+            msg = exc.args[0]
+            if isinstance(msg, bytes):
+                msg = msg.decode()
+            raise SystemExit(f"unknown path: {msg}") from exc
+        print(dist)
+        return
+    if args.cmd == "distance-matrix":  # cli.py:347-363
+        M = genome_distance_matrix(args.gfa, method=args.method, raw_bytes_id=args.raw_bytes_id, backend=args.backend,
+                                   verbose=args.verbose, device=args.device)
+        try:
+            save_matrix(M, Path(args.output), verbose=args.verbose, max_dense_gb=args.max_dense_gb)
+        except MemoryError as exc:
+            raise SystemExit(str(exc)) from exc
         return
     if args.cmd != "convert":
         parser.error(f"'{args.cmd}' is outside the GPU GFA->CSR path; use the reference gfa2network for it")

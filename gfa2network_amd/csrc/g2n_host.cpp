@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -317,6 +318,114 @@ int g2n_stats_from_path(const char* path, const g2n_options* opts, g2n_graph_sta
   struct Scope {
     explicit Scope(const g2n::StatsRequest* r) { g2n::set_stats_request(r); }
     ~Scope() { g2n::set_stats_request(nullptr); }
+  } scope(&req);
+  return build_from_path(path, &o, res);
+}
+
+// load_paths' own read of the file (the reference parses it once for the paths, once for the graph):
+// the plain bytes, or the text of the gunzip routes — on a gzip error the whole lines its reader
+// returned before raising, as the line loop over gzip.open sees them.
+int g2n_load_paths(const char* path, g2n_paths** out) {
+  if (!out || !path) return G2N_E_ARG;
+  *out = nullptr;
+  return g2n::guarded([&]() -> int {
+    const std::string p(path);
+    const bool gz = p.size() >= 3 && p.compare(p.size() - 3, 3, ".gz") == 0;
+    const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) {
+      g2n::set_last_error(p + ": " + std::strerror(errno));
+      return G2N_E_IO;
+    }
+    g2n::HostBuf raw;
+    size_t rlen = 0;
+    const int err = g2n::read_fd(fd, raw, &rlen);
+    ::close(fd);
+    if (err) {
+      g2n::set_last_error(p + ": " + std::strerror(err));
+      return G2N_E_IO;
+    }
+    std::unique_ptr<g2n_paths> ps(new g2n_paths());
+    if (!gz) {
+      g2n::scan_paths(raw.p, rlen, ps.get());
+    } else {
+      g2n::Inflated z;
+      size_t len = 0;
+      if (g2n::gunzip_parallel(raw.p, rlen, z)) {
+        len = z.total;
+      } else {
+        int sub = 0;
+        std::string msg;
+        z = g2n::Inflated();
+        len = g2n::gunzip_exact(raw.p, rlen, z, &sub, &msg) ? z.total : g2n::whole_lines(z);
+      }
+      g2n::HostBuf text;
+      text.alloc(len + 1);
+      if (len) g2n::fill_from(z)(0, text.p, len);
+      g2n::scan_paths(text.p, len, ps.get());
+    }
+    *out = ps.release();
+    return G2N_OK;
+  });
+}
+
+int g2n_distances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
+                            int64_t target, int32_t mode, void* out_tables, g2n_dist_info* info, int32_t* oriented,
+                            int64_t* missing_step, g2n_result** res) {
+  if (!res || !path || !paths || !info || !oriented || !missing_step) return G2N_E_ARG;
+  *res = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  std::memset(info, 0, sizeof(*info));
+  const int64_t n_paths = (int64_t)paths->name_offs.size() - 1;
+  if (source >= n_paths || (source >= 0 && (target < 0 || target >= n_paths))) return G2N_E_ARG;
+  g2n_options o;  // the plain graph's build, as g2n_stats_from_path's — with the names, which the steps are looked up in
+  g2n_options_init(&o);
+  o.directed = opts->directed != 0;
+  o.asymmetric = 1;
+  o.dtype = G2N_BOOL;
+  o.output = G2N_OUT_CSR;
+  o.want_node_names = 1;
+  o.device = opts->device;
+  o.unknown_warned = opts->unknown_warned;
+  o.test_flags = opts->test_flags;
+  g2n::DistRequest req{};
+  std::vector<uint8_t> pair_blob;
+  std::vector<int64_t> pair_offs{0}, pair_ptr{0};
+  if (source < 0) {  // every path a source: the K x K tables
+    req.step_blob = paths->steps.data();
+    req.step_offs = paths->step_offs.data();
+    req.path_ptr = paths->path_ptr.data();
+    req.K = (uint64_t)n_paths;
+    req.n_steps = req.n_source_steps = paths->step_offs.size() - 1;
+  } else {  // the source's steps, then the target's: 2 x 2 tables, only the source's steps must be nodes
+    for (const int64_t k : {source, target}) {
+      for (int64_t s = paths->path_ptr[k]; s < paths->path_ptr[k + 1]; s++) {
+        pair_blob.insert(pair_blob.end(), paths->steps.begin() + paths->step_offs[s],
+                         paths->steps.begin() + paths->step_offs[s + 1]);
+        pair_offs.push_back((int64_t)pair_blob.size());
+      }
+      pair_ptr.push_back((int64_t)pair_offs.size() - 1);
+    }
+    req.step_blob = pair_blob.data();
+    req.step_offs = pair_offs.data();
+    req.path_ptr = pair_ptr.data();
+    req.K = 2;
+    req.n_steps = pair_offs.size() - 1;
+    req.n_source_steps = (uint64_t)pair_ptr[1];
+  }
+  if (req.K && !out_tables) return G2N_E_ARG;
+  req.mode = mode;
+  req.check_ascii = opts->want_node_names != 0;
+  req.names_if_high = !req.check_ascii && o.directed;
+  req.tables = out_tables;
+  req.info = info;
+  req.oriented = oriented;
+  req.missing_step = missing_step;
+  *oriented = 0;
+  *missing_step = -1;
+  struct Scope {
+    explicit Scope(const g2n::DistRequest* r) { g2n::set_dist_request(r); }
+    ~Scope() { g2n::set_dist_request(nullptr); }
   } scope(&req);
   return build_from_path(path, &o, res);
 }

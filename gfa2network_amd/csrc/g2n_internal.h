@@ -10,7 +10,19 @@
 
 #include "../../include/g2n.h"
 
+// g2n_load_paths' result (g2n_paths.cpp): the paths in first-occurrence order, each with the steps
+// of its last record; path k's steps are steps [path_ptr[k], path_ptr[k + 1]) of step_offs.
+struct g2n_paths {
+  std::vector<uint8_t> names, steps;
+  std::vector<int64_t> name_offs{0}, step_offs{0}, path_ptr{0};
+  int64_t bad_line = -1;           // the first P / O record with a non-ASCII name or step (0-based line)
+  std::vector<uint8_t> bad_bytes;  // that name or step
+};
+
 namespace g2n {
+
+// the P / O records of len bytes of GFA text into *out (g2n_paths.cpp)
+void scan_paths(const uint8_t* text, size_t len, g2n_paths* out);
 
 // Internal failure carrying a G2N_E_* status and a message for g2n_last_error().
 struct Failure : std::runtime_error {
@@ -88,6 +100,26 @@ struct StatsRequest {
   bool check_ascii;  // a node key with a byte >= 0x80: status G2N_E_UNICODE, err_line -1 (include/g2n.h)
 };
 void set_stats_request(const StatsRequest* req);  // nullptr: none (thread-local)
+
+// g2n_distances_from_path: the same, for path distances.  The build's CSR and names stay on the
+// device; the K paths' step names (host blob + offsets, sources first) are looked up in the names
+// there, and g2n_csr_path_distances runs on the ids.  Only the tables and the scalars come back.
+struct DistRequest {
+  const uint8_t* step_blob;   // host
+  const int64_t* step_offs;   // host, n_steps + 1
+  const int64_t* path_ptr;    // host, K + 1 offsets into the steps
+  uint64_t K, n_steps;
+  uint64_t n_source_steps;    // steps [0, n_source_steps) must be nodes (else *missing_step = the first that is not)
+  int32_t mode;
+  bool check_ascii;           // as StatsRequest::check_ascii
+  bool names_if_high;         // raw keys of a directed graph: when one has a byte >= 0x80 the names come back too
+                              // (the reference's orientation check decodes keys as UTF-8 until one is oriented)
+  void* tables;               // host, out
+  g2n_dist_info* info;
+  int32_t* oriented;          // out: 1 when a node key ends in ":+" or ":-"
+  int64_t* missing_step;      // out: -1, or a source step that is no node (nothing was searched then)
+};
+void set_dist_request(const DistRequest* req);  // nullptr: none (thread-local)
 
 // Parallel multi-member gunzip.  Members are found by their header bytes and inflated
 // speculatively on host_threads() threads; the chain of members from byte 0 (zero padding

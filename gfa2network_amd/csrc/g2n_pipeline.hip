@@ -25,6 +25,7 @@
 #include "g2n_inflate.hip"
 #include "g2n_keyset.hip"
 #include "g2n_stats.hip"
+#include "g2n_dist.hip"
 
 #define G2N_HIP(call)                                                                                      \
   do {                                                                                                     \
@@ -45,6 +46,9 @@ enum Slot {
   S_PCNT, S_POFF, S_PGRP, S_BSTART, S_SCANST, S_RBOUND, S_ROWSP, S_COLSP, S_TLEAN, S_ZIN, S_ZMEM, S_ZBAD, S_RSK, S_RSV, S_RSCNT, S_RSOFF,
   S_GCNT, S_TCN, S_INDPTR64, S_INDICES64, S_WENC, S_W1, S_W2, S_TVAL, S_PW0, S_PW1, S_BSTARTA, S_DIRECT, S_RTOT, S_SCANST2, S_EWP, S_TLIST, S_TNB, S_WENCP,
   S_STPARENT, S_STCOL, S_STDIAG, S_STLONG, S_STOUT, S_STIP, S_STIX,  // g2n_csr_stats (g2n_stats.hip)
+  S_DSEEN, S_DNEXT, S_DQUEUE, S_DQMASK, S_DLONG, S_DSTATE, S_DCNT, S_DMPTR, S_DCUR, S_DMPATH, S_DSPATH, S_DDONE,
+  S_DTAB, S_DPP, S_DPN,  // g2n_csr_path_distances (g2n_dist.hip)
+  S_DFLAG, S_DKS, S_DSBLOB, S_DSOFFS, S_DIDS,  // g2n_distances_from_path: the step lookup
   S_NSLOTS
 };
 
@@ -2371,12 +2375,220 @@ int csr_stats_host(const void* indptr, const void* indices, int32_t index_width,
   return G2N_OK;
 }
 
+// --------------------------------------------------------- path distances ------
+// g2n_csr_path_distances on c's stream (the caller holds c's lock and opened the call); tables: device.
+template <class I>
+static void path_distances_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz,
+                             const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, uint64_t steps, bool mean,
+                             void* tables, g2n_dist_info* info) {
+  auto* st = dget<DistState>(c, S_DSTATE, 1);
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  // ---- the caller's arrays, checked whole; the steps' paths and the nodes' step counts
+  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  auto* mem_ptr = dget<uint32_t>(c, S_DMPTR, n + 1);
+  auto* cursor = dget<uint32_t>(c, S_DCUR, n + 1);
+  auto* mem_path = dget<uint32_t>(c, S_DMPATH, steps);
+  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
+  G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
+                     indices, n, nnz, st);
+  hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
+  if (steps)
+    hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
+                       step_path, cnt, st);
+  if (read_dev(c, st).bad)
+    throw Failure(G2N_E_ARG, "g2n_csr_path_distances: indptr / indices / path_ptr / path_nodes out of range");
+  // ---- membership: the steps sorted by node
+  scan_excl<uint32_t, uint32_t>(c, cnt, mem_ptr, n + 1);
+  G2N_HIP(hipMemcpyAsync(cursor, mem_ptr, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  if (steps)
+    hipLaunchKernelGGL(k_dist_fill, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
+                       (const uint32_t*)step_path, cursor, mem_path);
+  // ---- tables
+  DistAcc acc{mem_ptr, mem_path, nullptr, nullptr, nullptr, nullptr, K, 0};
+  if (mean) {
+    acc.S = (unsigned long long*)tables;
+    acc.C = acc.S + K * K;
+    G2N_HIP(hipMemsetAsync(tables, 0, K * K * 16, c->stream));
+  } else {
+    acc.D = (uint32_t*)tables;
+    acc.done = dget<unsigned long long>(c, S_DDONE, K);
+    G2N_HIP(hipMemsetAsync(tables, 0xFF, K * K * 4, c->stream));
+  }
+  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
+  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
+  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
+  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
+  std::vector<int64_t> h_ptr(K + 1);
+  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  const unsigned gn = std::min(grid_for(n), gcap);
+  int64_t launches = 0, levels = 0, batches = 0;
+  for (uint64_t base = 0; base < K; base += 64, batches++) {
+    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[std::min<uint64_t>(base + 64, K)];
+    acc.base = (uint32_t)base;
+    G2N_HIP(hipMemsetAsync(seen, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
+    if (acc.done) G2N_HIP(hipMemsetAsync(acc.done, 0, K * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+    if (s1 > s0) {
+      hipLaunchKernelGGL(k_dist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
+                         (const uint32_t*)step_path, (uint32_t)base, seen, next);
+      launches++;
+    }
+    uint32_t L = 0;
+    for (bool more = s1 > s0; more;) {
+      // wide: level L's frontier from next (count, n_long, pending cleared first)
+      G2N_HIP(hipMemsetAsync(st, 0, 3 * sizeof(uint32_t), c->stream));
+      hipLaunchKernelGGL(k_dist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc, st);
+      launches++;
+      DistState h = read_dev(c, st);
+      if (h.count == 0) break;
+      if (h.count > kDistNarrowCap) {
+        hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(h.count), gcap)), dim3(256), 0, c->stream, indptr,
+                           indices, n, nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
+                           long_rows, long_cap, st);
+        hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
+                           nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
+                           (const uint32_t*)long_rows, long_cap, st);
+        launches += 2;
+        L++;
+        continue;
+      }
+      // narrow: one workgroup carries it until it empties, overflows or has run its budget
+      for (;;) {
+        hipLaunchKernelGGL(k_dist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n, nnz, seen,
+                           next, queue, qmask, acc, st, kDistLevelBudget);
+        launches++;
+        h = read_dev(c, st);
+        if (h.pending) {
+          L = h.level;
+          break;
+        }
+        if (h.count == 0) {
+          more = false;
+          break;
+        }
+        if (h.count > kDistNarrowCap) throw Failure(G2N_E_DEVICE, "g2n_csr_path_distances: frontier state");
+      }
+    }
+    const DistState h = read_dev(c, st);
+    if (h.bad) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: indptr / indices out of range");
+    levels = std::max<int64_t>(levels, h.last_level);
+  }
+  info->levels = levels;
+  info->launches = launches;
+  info->batches = batches;
+}
+
+static void path_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
+                           uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
+                           void* tables, g2n_dist_info* info) {
+  if (index_width != 4 && index_width != 8)
+    throw Failure(G2N_E_ARG, "g2n_csr_path_distances: index_width must be 4 or 8");
+  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: unknown mode");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: 2^32-1 or more entries");
+  std::memset(info, 0, sizeof(*info));
+  if (K == 0) return;
+  if (!path_ptr || !tables) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: null array");
+  if ((n && !indptr) || (nnz && !indices)) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: null array");
+  if (n == 0 && nnz) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: entries without rows");
+  int64_t ends[2];
+  G2N_HIP(hipMemcpyAsync(&ends[0], path_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipMemcpyAsync(&ends[1], path_ptr + K, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  if (ends[0] != 0 || ends[1] < 0) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: path_ptr out of range");
+  const uint64_t steps = (uint64_t)ends[1];
+  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: 2^32-1 or more steps");
+  if (steps && !path_nodes) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: null array");
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (auto& x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  if (index_width == 4)
+    path_distances_t<int32_t>(c, (const int32_t*)indptr, (const int32_t*)indices, n, nnz, path_ptr, path_nodes, K, steps,
+                              mode == G2N_DIST_MEAN, tables, info);
+  else
+    path_distances_t<int64_t>(c, (const int64_t*)indptr, (const int64_t*)indices, n, nnz, path_ptr, path_nodes, K, steps,
+                              mode == G2N_DIST_MEAN, tables, info);
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  info->ms_bfs = ms;
+}
+
+// bytes of the tables of K paths (mean: S then C, uint64 each; min: D, uint32); 0 = past 2^63
+static uint64_t dist_table_bytes(uint64_t K, int32_t mode) {
+  if (K >= (1ull << 29)) return 0;
+  return K * K * (mode == G2N_DIST_MEAN ? 16 : 4);
+}
+
+// the three K x K tables of one call must fit the device's free memory
+static void dist_check_k(uint64_t K, int32_t mode) {
+  size_t f = 0, t = 0;
+  G2N_HIP(hipMemGetInfo(&f, &t));
+  const uint64_t want = dist_table_bytes(K, mode);
+  if ((K && !want) || want + K * 8 > f)
+    throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: the K x K tables of " + std::to_string(K) +
+                                         " paths exceed the device's free memory");
+}
+
+int csr_path_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                            const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
+                            void* out_tables, int32_t device, g2n_dist_info* info) {
+  if (index_width != 4 && index_width != 8)
+    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: index_width must be 4 or 8");
+  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN)
+    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: unknown mode");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_host: 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_host: 2^32-1 or more entries");
+  if (!indptr || (nnz && !indices) || !path_ptr || (K && !out_tables))
+    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: null array");
+  if (path_ptr[0] != 0 || path_ptr[K] < 0 || (path_ptr[K] && !path_nodes))
+    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: path_ptr out of range");
+  const uint64_t steps = (uint64_t)path_ptr[K];
+  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_host: 2^32-1 or more steps");
+  g2n_context* c = shared_context(device);
+  std::lock_guard<std::mutex> lk(c->mu);
+  enter_call(c);
+  G2N_HIP(hipSetDevice(c->device));
+  clear_call_state(c);
+  dist_check_k(K, mode);
+  const size_t w = (size_t)index_width;
+  void* dip = dbuf(c, S_STIP, (size_t)(n + 1) * w);
+  void* dix = dbuf(c, S_STIX, (size_t)nnz * w);
+  auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
+  auto* dpn = dget<int64_t>(c, S_DPN, steps);
+  const uint64_t tbytes = dist_table_bytes(K, mode);
+  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
+  G2N_HIP(hipMemcpyAsync(dip, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
+  if (nnz) G2N_HIP(hipMemcpyAsync(dix, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
+  G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
+  path_distances(c, dip, dix, index_width, n, nnz, dpp, dpn, K, mode, dtab, info);
+  if (tbytes) G2N_HIP(hipMemcpyAsync(out_tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  shrink_shared(c);
+  return G2N_OK;
+}
+
 static thread_local const StatsRequest* t_stats_request = nullptr;
 void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
+static thread_local const DistRequest* t_dist_request = nullptr;
+void set_dist_request(const DistRequest* req) { t_dist_request = req; }
 
-// A stats build's result (g2n_stats_from_path): D's CSR stays on the device, the statistics are
-// taken from it there, and H receives D's scalars — plus the one key the ASCII check objects to.
-static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, const StatsRequest& q) {
+// H's result as D's scalars, no matrix and no names (a stats or distance request's build)
+static void scalars_result(g2n_context* c, const g2n_result& D, HostResult* H) {
   g2n_result& R = H->r;
   std::memcpy(&R, &D, sizeof(g2n_result));
   R.priv_ = H;
@@ -2387,18 +2599,20 @@ static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, con
   R.rows = R.cols = R.indptr = R.indices = R.data = nullptr;
   if (D.err_detail) R.err_detail = (const uint8_t*)download(c, H->detail, D.err_detail, (size_t)D.err_detail_len);
   G2N_HIP(hipStreamSynchronize(c->stream));
-  if (D.status != G2N_OK) return;
-  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_stats_from_path: the build returned no CSR");
-  csr_stats(c, D.indptr, D.indices, D.index_width, (uint64_t)D.n_nodes, (uint64_t)D.nnz, q.directed, q.out);
-  *q.n_paths = D.n_records - D.n_edges - (int64_t)c->last_n_segs;
-  if (!q.check_ascii || !D.names_blob || !D.names_bytes || !D.n_nodes) return;
+}
+
+// The graph path's ASCII decode of node keys after a clean build: true (H's result then carries
+// G2N_E_UNICODE, err_line -1, the lowest such node id and its key) when a key has a byte >= 0x80.
+static bool ascii_key_check(g2n_context* c, const g2n_result& D, HostResult* H) {
+  g2n_result& R = H->r;
+  if (!D.names_blob || !D.names_bytes || !D.n_nodes) return false;
   StatsOut* so = stats_out_reset(c);
   const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
   hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
   hipLaunchKernelGGL(k_high_owner, dim3(1), dim3(64), 0, c->stream, D.names_offsets, (uint64_t)D.n_nodes, so);
   const StatsOut h = read_dev(c, so);
-  if (h.high_off == ~0ull) return;
-  if (h.high_id < 0 || h.high_id >= D.n_nodes) throw Failure(G2N_E_DEVICE, "g2n_stats_from_path: key lookup failed");
+  if (h.high_off == ~0ull) return false;
+  if (h.high_id < 0 || h.high_id >= D.n_nodes) throw Failure(G2N_E_DEVICE, "node keys: key lookup failed");
   int64_t span[2];
   G2N_HIP(hipMemcpyAsync(span, D.names_offsets + h.high_id, sizeof(span), hipMemcpyDeviceToHost, c->stream));
   G2N_HIP(hipStreamSynchronize(c->stream));
@@ -2409,12 +2623,117 @@ static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, con
   R.err_line = -1;
   R.err_index = h.high_id;
   set_last_error("a node key is not ASCII (the graph path decodes node keys as ASCII)");
+  return true;
 }
 
-// the outputs of one host build: the matrix and names, or (a stats request) the statistics' scalars
+// A stats build's result (g2n_stats_from_path): D's CSR stays on the device, the statistics are
+// taken from it there, and H receives D's scalars — plus the one key the ASCII check objects to.
+static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, const StatsRequest& q) {
+  scalars_result(c, D, H);
+  if (D.status != G2N_OK) return;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_stats_from_path: the build returned no CSR");
+  csr_stats(c, D.indptr, D.indices, D.index_width, (uint64_t)D.n_nodes, (uint64_t)D.nnz, q.directed, q.out);
+  *q.n_paths = D.n_records - D.n_edges - (int64_t)c->last_n_segs;
+  if (q.check_ascii) (void)ascii_key_check(c, D, H);
+}
+
+// A distance build's result (g2n_distances_from_path): D's CSR and names stay on the device.  The
+// names go into a key table over their own blob (ids = node ids), the request's step names are
+// looked up in it in one launch, and g2n_csr_path_distances runs on the ids.
+static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, const DistRequest& q) {
+  scalars_result(c, D, H);
+  *q.oriented = 0;
+  *q.missing_step = -1;
+  if (D.status != G2N_OK) return;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_distances_from_path: the build returned no CSR");
+  const uint64_t n = (uint64_t)D.n_nodes;
+  if (n && (!D.names_blob || !D.names_offsets)) throw Failure(G2N_E_DEVICE, "g2n_distances_from_path: no names");
+  if (q.check_ascii && ascii_key_check(c, D, H)) return;
+  if (q.names_if_high && n && D.names_bytes) {
+    StatsOut* so = stats_out_reset(c);
+    const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
+    hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
+    if (read_dev(c, so).high_off != ~0ull) {
+      g2n_result& R = H->r;
+      const int64_t* offs = (const int64_t*)download(c, H->offs, D.names_offsets, (size_t)(n + 1) * sizeof(int64_t));
+      G2N_HIP(hipStreamSynchronize(c->stream));
+      R.names_blob = (const uint8_t*)download(c, H->blob, D.names_blob, (size_t)offs[n]);
+      R.names_offsets = offs;
+      R.names_bytes = D.names_bytes;
+      G2N_HIP(hipStreamSynchronize(c->stream));
+    }
+  }
+  if (q.n_steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_distances_from_path: 2^32-1 or more steps");
+  dist_check_k(q.K, q.mode);
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (auto& x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  // ---- the orientation flag and the first missing source step
+  auto* flags = dget<unsigned long long>(c, S_DFLAG, 2);  // [0] oriented, [1] the first missing source step
+  G2N_HIP(hipMemsetAsync(flags, 0, 8, c->stream));
+  G2N_HIP(hipMemsetAsync(flags + 1, 0xFF, 8, c->stream));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  if (n)
+    hipLaunchKernelGGL(k_key_oriented, dim3(std::min(grid_for(n), gcap)), dim3(256), 0, c->stream, D.names_blob,
+                       D.names_offsets, n, (uint32_t*)flags);
+  // ---- the key table over the names' own blob, and the steps looked up in it
+  uint64_t cap = 1024;
+  while (cap < 2 * n) cap *= 2;
+  auto* table = dget<KsEntry>(c, S_DKS, cap);
+  G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(KsEntry), c->stream));
+  if (n)
+    hipLaunchKernelGGL(k_ks_insert, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, D.names_blob, D.names_offsets, n,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int64_t*)nullptr, (uint64_t)0,
+                       (uint64_t)0, table, cap - 1, (uint8_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr, 1);
+  const uint64_t sbytes = (uint64_t)q.step_offs[q.n_steps];
+  auto* sblob = dget<uint8_t>(c, S_DSBLOB, sbytes + 16);
+  auto* soffs = dget<int64_t>(c, S_DSOFFS, q.n_steps + 1);
+  auto* ids = dget<uint32_t>(c, S_DIDS, q.n_steps);
+  auto* fresh = dget<uint32_t>(c, S_DCUR, q.n_steps);  // (scratch: path_distances_t takes the slot afterwards)
+  auto* dpp = dget<int64_t>(c, S_DPP, q.K + 1);
+  auto* dpn = dget<int64_t>(c, S_DPN, q.n_steps);
+  if (sbytes) G2N_HIP(hipMemcpyAsync(sblob, q.step_blob, sbytes, hipMemcpyHostToDevice, c->stream));
+  G2N_HIP(hipMemcpyAsync(soffs, q.step_offs, (q.n_steps + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  G2N_HIP(hipMemcpyAsync(dpp, q.path_ptr, (q.K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (q.n_steps) {
+    hipLaunchKernelGGL(k_ks_lookup, dim3(grid_for(q.n_steps, 256)), dim3(256), 0, c->stream, (const uint8_t*)sblob,
+                       (const int64_t*)soffs, q.n_steps, (const KsEntry*)table, cap - 1, D.names_blob, ids, fresh);
+    hipLaunchKernelGGL(k_dist_resolved, dim3(grid_for(q.n_steps)), dim3(256), 0, c->stream, (const uint32_t*)ids,
+                       q.n_steps, q.n_source_steps, dpn, flags + 1);
+  }
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  unsigned long long h[2];
+  G2N_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *q.oriented = (uint32_t)h[0] != 0;
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  if (h[1] != ~0ull) {
+    *q.missing_step = (int64_t)h[1];
+    std::memset(q.info, 0, sizeof(*q.info));
+    q.info->ms_resolve = ms;
+    return;
+  }
+  const uint64_t tbytes = dist_table_bytes(q.K, q.mode);
+  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
+  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, q.K, q.mode, dtab, q.info);
+  q.info->ms_resolve = ms;
+  if (tbytes) G2N_HIP(hipMemcpyAsync(q.tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// the outputs of one host build: the matrix and names, or (a stats / distance request) scalars
 static void host_result(g2n_context* c, const g2n_result& D, HostResult* H) {
   if (t_stats_request)
     stats_result(c, D, H, *t_stats_request);
+  else if (t_dist_request)
+    dist_result(c, D, H, *t_dist_request);
   else
     download_result(c, D, H);
 }
@@ -3319,6 +3638,28 @@ int g2n_csr_stats_host(const void* indptr, const void* indices, int32_t index_wi
   if (!out) return G2N_E_ARG;
   return g2n::guarded(
       [&] { return g2n::csr_stats_host(indptr, indices, index_width, n, nnz, directed, device, out); });
+}
+
+int g2n_csr_path_distances(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width, uint64_t n,
+                           uint64_t nnz, const int64_t* d_path_ptr, const int64_t* d_path_nodes, uint64_t K, int32_t mode,
+                           void* d_out_tables, g2n_dist_info* info) {
+  if (!info) return G2N_E_ARG;
+  G2N_CTX_CALL(ctx, {
+    g2n::dist_check_k(K, mode);
+    g2n::path_distances(ctx, d_indptr, d_indices, index_width, n, nnz, d_path_ptr, d_path_nodes, K, mode, d_out_tables,
+                        info);
+  });
+  return G2N_OK;
+}
+
+int g2n_csr_path_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                                const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
+                                void* out_tables, int32_t device, g2n_dist_info* info) {
+  if (!info) return G2N_E_ARG;
+  return g2n::guarded([&] {
+    return g2n::csr_path_distances_host(indptr, indices, index_width, n, nnz, path_ptr, path_nodes, K, mode, out_tables,
+                                        device, info);
+  });
 }
 
 int g2n_device_memory(int32_t device, uint64_t* free_bytes, uint64_t* total_bytes) {

@@ -495,6 +495,74 @@ int g2n_csr_stats_host(const void *indptr, const void *indices, int32_t index_wi
 int g2n_stats_from_path(const char *path, const g2n_options *opts, g2n_graph_stats *out, int64_t *n_paths,
                         g2n_result **res);
 
+/* ---- path distances (gfa2network/analysis.py genome_distance_matrix) ---------------------------
+ * Hop distances between K node lists ("paths") over a CSR's structure: every stored (u, v) is an
+ * edge u -> v of weight 1, the values are never read.  Path k's steps are
+ * path_nodes[path_ptr[k] .. path_ptr[k + 1]) (node ids, in list order, duplicates kept);
+ * path_ptr[0] = 0.  d_i(v) = hops from the nearest step of path i to v (0 on its own steps).  One
+ * bit-parallel breadth-first search serves 64 paths (g2n_dist.hip).  The tables are row-major K x K:
+ *   G2N_DIST_MIN   D, uint32: D[i][j] = min over the steps v of j of d_i(v); 0xFFFFFFFF = none reached
+ *   G2N_DIST_MEAN  S then C, uint64 each: S[i][j] = the sum of d_i(v) over the steps v of j that i
+ *                  reaches, each occurrence counted; C[i][j] = how many those are
+ * (the reference's symmetric matrix: min takes D[i][j] for i < j; mean takes (S[i][j] + S[j][i]) /
+ * (C[i][j] + C[j][i])).  info: levels = the deepest level any search reached, launches = kernels
+ * launched by the searches, batches = ceil(K / 64); ms_*: hipEvent times (ms_resolve: the lookup of
+ * step names, 0 where the caller passes node ids). */
+#define G2N_DIST_MIN 0
+#define G2N_DIST_MEAN 1
+typedef struct g2n_dist_info {
+  int64_t levels, launches, batches;
+  double ms_resolve, ms_bfs; /* hipEvent, pipeline stream */
+} g2n_dist_info;
+
+/* load_paths (analysis.py:164-177), host only: the P / O records of the named file (plain, or
+ * gunzipped when the name ends in ".gz") as names (blob + n_paths + 1 offsets, first-occurrence
+ * order; a repeated name takes its last record's steps) and steps (blob + offsets; path k's steps
+ * are steps path_ptr[k] .. path_ptr[k + 1]): field 2 cut at commas, one trailing '+' or '-' removed
+ * from each, an empty field being one empty step.  bad_line = the 0-based line of the first P / O
+ * record whose name or step has a byte >= 0x80 (-1: none) and bad_bytes that name or step — what
+ * .decode("ascii") raises on, for the caller to order against a build's err_line.  The parser's own
+ * errors are the build's to report: a record with fewer than three fields is skipped here, and on
+ * a gzip error the whole lines read before it are scanned.  G2N_E_IO when the file cannot be read.
+ * The pointers live until g2n_paths_free. */
+typedef struct g2n_paths g2n_paths;
+int g2n_load_paths(const char *path, g2n_paths **out);
+void g2n_paths_get(const g2n_paths *p, const uint8_t **names, const int64_t **name_offs, uint64_t *n_paths,
+                   const uint8_t **steps, const int64_t **step_offs, const int64_t **path_ptr, int64_t *bad_line,
+                   const uint8_t **bad_bytes, uint64_t *bad_len);
+void g2n_paths_free(g2n_paths *p);
+
+/* genome_distance_matrix / `distance --path` (analysis.py:116-141, 180-272): the input is ingested
+ * and built as by g2n_stats_from_path (of opts only directed, want_node_names, device,
+ * unknown_warned and test_flags are read), the CSR and the node names stay on the device, the
+ * paths' step names are looked up in the names there and g2n_csr_path_distances runs on the ids.
+ * source < 0: every path of `paths` is searched, out_tables (host) = the K x K tables of all K
+ * paths.  source >= 0: the two paths (source, target), out_tables = their 2 x 2 tables — cell
+ * [0][1] is the answer; only the source's steps must be nodes, a target step that is none is
+ * never reached.  *oriented = 1 when a node key ends in ":+" or ":-" (the reference's orientation
+ * warning).  *missing_step = -1, or the first searched step that is no node (an index into the
+ * steps of `paths`; source >= 0: into the source's steps): nothing is searched then.  *res as
+ * g2n_stats_from_path's, want_node_names = 1 asking for the same ASCII check of node keys. */
+int g2n_distances_from_path(const char *path, const g2n_options *opts, const g2n_paths *paths, int64_t source,
+                            int64_t target, int32_t mode, void *out_tables, g2n_dist_info *info, int32_t *oriented,
+                            int64_t *missing_step, g2n_result **res);
+
+/* DEVICE pointers on ctx's device (index_width 4 or 8 bytes per indptr / indices element, path
+ * arrays int64; a step of -1 is no node: never reached, no source); d_out_tables holds K * K * 4 (min) or K * K * 16 (mean) bytes; scratch from ctx's
+ * arena; returns after the stream drained.  G2N_E_UNSUPPORTED for n >= 2^31 - 1, nnz >= 2^32 - 1,
+ * 2^32 - 1 or more steps, or tables of K paths past the device's free memory; G2N_E_ARG when indptr
+ * or path_ptr is not a non-decreasing map into its range or an index or step is outside [0, n)
+ * (nothing out of range is ever addressed). */
+int g2n_csr_path_distances(g2n_context *ctx, const void *d_indptr, const void *d_indices, int32_t index_width,
+                           uint64_t n, uint64_t nnz, const int64_t *d_path_ptr, const int64_t *d_path_nodes, uint64_t K,
+                           int32_t mode, void *d_out_tables, g2n_dist_info *info);
+
+/* The same for arrays in HOST memory (out_tables too): uploaded to `device` (the host entry
+ * points' cached context). */
+int g2n_csr_path_distances_host(const void *indptr, const void *indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                                const int64_t *path_ptr, const int64_t *path_nodes, uint64_t K, int32_t mode,
+                                void *out_tables, int32_t device, g2n_dist_info *info);
+
 #ifdef __cplusplus
 }
 #endif
