@@ -43,6 +43,7 @@ EXPORTED = [
     "g2n_csr_stats", "g2n_csr_stats_host", "g2n_stats_from_path",
     "g2n_csr_path_distances", "g2n_csr_path_distances_host", "g2n_load_paths", "g2n_paths_get", "g2n_paths_free",
     "g2n_distances_from_path",
+    "g2n_seq_distance_from_path", "g2n_seq_hits_get", "g2n_seq_hits_names", "g2n_seq_hits_free",
 ]
 
 
@@ -158,6 +159,23 @@ class DistInfo(ctypes.Structure):
         ("launches", ctypes.c_int64),
         ("batches", ctypes.c_int64),
         ("ms_resolve", ctypes.c_double),
+        ("ms_bfs", ctypes.c_double),
+    ]
+
+
+class SeqInfo(ctypes.Structure):
+    """g2n_seq_info (include/g2n.h)."""
+
+    _fields_ = [
+        ("n_s_lines", ctypes.c_int64),
+        ("n_with_seq", ctypes.c_int64),
+        ("candidates_a", ctypes.c_int64),
+        ("candidates_b", ctypes.c_int64),
+        ("levels", ctypes.c_int64),
+        ("launches", ctypes.c_int64),
+        ("batches", ctypes.c_int64),
+        ("ms_scan", ctypes.c_double),
+        ("ms_match", ctypes.c_double),
         ("ms_bfs", ctypes.c_double),
     ]
 
@@ -340,6 +358,17 @@ def load() -> ctypes.CDLL:
                                             ctypes.POINTER(DistInfo), ctypes.POINTER(I32), ctypes.POINTER(I64),
                                             ctypes.POINTER(ctypes.POINTER(Result))]
     lib.g2n_distances_from_path.restype = ctypes.c_int
+    lib.g2n_seq_distance_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), ctypes.c_char_p, U64,
+                                               ctypes.c_char_p, U64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(P),
+                                               ctypes.POINTER(SeqInfo), ctypes.POINTER(I32),
+                                               ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_seq_distance_from_path.restype = ctypes.c_int
+    lib.g2n_seq_hits_get.argtypes = [P] + [P] * 4
+    lib.g2n_seq_hits_get.restype = None
+    lib.g2n_seq_hits_names.argtypes = [P, P, P]
+    lib.g2n_seq_hits_names.restype = None
+    lib.g2n_seq_hits_free.argtypes = [P]
+    lib.g2n_seq_hits_free.restype = None
     for f in ("g2n_keyset_create", "g2n_keyset_add", "g2n_keyset_view", "g2n_partition_keys", "g2n_dedup_keys", "g2n_gather_keys", "g2n_remap_pairs", "g2n_route_triplets", "g2n_csr_from_coo_pair",
               "g2n_context_group_slots", "g2n_route_group_slots", "g2n_csr_from_group_slots",
               "g2n_upload_file_range", "g2n_count_device", "g2n_build_decimal_range", "g2n_order_keys",
@@ -636,6 +665,41 @@ def distances_from_path(path: str, opts: Options, paths: Paths, source: int, tar
     d = {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
          "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
     return _from_result(res, rc), tuple(out), d, bool(oriented.value), int(missing.value)
+
+
+def seq_distance_from_path(path: str, opts: Options, seq_a: bytes, seq_b: bytes):
+    """g2n_seq_distance_from_path: (the build's result without a matrix, the distance — 0xFFFFFFFF:
+    none reached or a set is empty —, [ids_a, ids_b]: the ascending int64 ids of the nodes that carry
+    seq_a and seq_b, [keys_a, keys_b]: those nodes' keys as bytes, the g2n_seq_info fields, the
+    orientation flag).  All but the result are meaningful only when the status is OK."""
+    lib = load()
+    dist, info, oriented = ctypes.c_uint32(0xFFFFFFFF), SeqInfo(), ctypes.c_int32(0)
+    hits, res = ctypes.c_void_p(), ctypes.POINTER(Result)()
+    a, b = bytes(seq_a), bytes(seq_b)
+    rc = lib.g2n_seq_distance_from_path(os.fsencode(path), ctypes.byref(opts), a, len(a), b, len(b),
+                                        ctypes.byref(dist), ctypes.byref(hits), ctypes.byref(info),
+                                        ctypes.byref(oriented), ctypes.byref(res))
+    ids = [np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)]
+    keys: list[list[bytes]] = [[], []]
+    if hits:
+        try:
+            P8, P64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64)
+            pa, pb, na, nb = P64(), P64(), ctypes.c_uint64(0), ctypes.c_uint64(0)
+            lib.g2n_seq_hits_get(hits, ctypes.byref(pa), ctypes.byref(na), ctypes.byref(pb), ctypes.byref(nb))
+            for k, (p, n) in enumerate(((pa, na.value), (pb, nb.value))):
+                if n:
+                    ids[k] = np.ctypeslib.as_array(p, shape=(n,)).astype(np.int64, copy=True)
+            blob, offs = P8(), P64()
+            lib.g2n_seq_hits_names(hits, ctypes.byref(blob), ctypes.byref(offs))
+            t = na.value + nb.value
+            o = np.ctypeslib.as_array(offs, shape=(t + 1,)).tolist()
+            text = ctypes.string_at(blob, o[t]) if o[t] else b""
+            names = [text[o[i]:o[i + 1]] for i in range(t)]
+            keys = [names[:na.value], names[na.value:]]
+        finally:
+            lib.g2n_seq_hits_free(hits)
+    d = {f: (float if f.startswith("ms_") else int)(getattr(info, f)) for f, _t in SeqInfo._fields_}
+    return _from_result(res, rc), int(dist.value), ids, keys, d, bool(oriented.value)
 
 
 BAND_ENTRIES = 2**31 - 2 # entries one g2n_coo_to_csr_band call takes (the weighted row-sum path's limit)

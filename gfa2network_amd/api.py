@@ -40,7 +40,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
            "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "load_paths", "genome_distance", "genome_distance_matrix",
-           "NodeNotFound", "NetworkXNoPath"]
+           "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
 # build's device working set is at most about this many bytes per input byte (the lean decimal-id
@@ -1071,6 +1071,55 @@ def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id
     if d == 0xFFFFFFFF:
         raise NetworkXNoPath("no path between node sets")
     return d
+
+
+def _seq_pass(path, seq_a, seq_b, directed: bool, raw_bytes_id: bool, verbose: bool, device: int, who: str):
+    """The one GPU pass of sequence_distance / sequence_nodes: the build's errors and warnings, the
+    orientation warning, then KeyError for a sequence no node carries (analysis.py:103-105: repr of
+    each missing argument as passed).  Returns (distance or 0xFFFFFFFF, [keys_a, keys_b], info)."""
+    p = _named_file(path, who)
+    _stats_one_piece(p, device, who, "path_distances")
+    a = seq_a if isinstance(seq_a, bytes) else seq_a.encode()
+    b = seq_b if isinstance(seq_b, bytes) else seq_b.encode()
+    opts = _dist_opts(directed, raw_bytes_id, device)
+    raw, dist, _ids, keys, info, oriented = nat.seq_distance_from_path(p, opts, a, b)
+    _graph_pass(raw, raw_bytes_id, verbose, path)
+    if directed:
+        _warn_oriented(raw, oriented)
+    missing = [repr(x) for x, k in ((seq_a, keys[0]), (seq_b, keys[1])) if not k]
+    if missing:
+        raise KeyError(f"sequence(s) {', '.join(missing)} not found")
+    if not raw_bytes_id:
+        keys = [[k.decode("ascii") for k in ks] for ks in keys]
+    return dist, keys, info
+
+
+def sequence_distance(path, seq_a, seq_b, *, directed: bool = True, raw_bytes_id: bool = False,
+                      verbose: bool = False, device: int = 0, return_info: bool = False):
+    """``sequence_distance`` (gfa2network/analysis.py:68-113) / ``gfa2network distance GFA --seq A B``
+    (cli.py:308-321) on a file where the reference takes a graph built with ``store_seq=True``: the
+    fewest hops (an int) from any node whose sequence is ``seq_a`` to any node whose sequence is
+    ``seq_b`` (``str`` encoded as UTF-8), 0 when the two sets meet.  A node's sequence is that of the
+    last S record of its name that has one (parser.py:135-163, builders.py:164-189).  The file is
+    parsed once: its bytes, the CSR and the node names stay in HBM, the S records are matched there
+    (g2n_seq.hip) and the two node sets go to the path-distance search; no sequence comes back.
+    After the build's own errors and warnings: the orientation warning on a directed graph,
+    KeyError("sequence(s) 'X' not found"), NetworkXNoPath("no path between sequences").  Stdin and
+    file objects raise NotImplementedError.  ``device`` and ``return_info`` (also return the
+    g2n_seq_info fields) are extensions."""
+    dist, _keys, info = _seq_pass(path, seq_a, seq_b, directed, raw_bytes_id, verbose, device, "sequence_distance")
+    if dist == 0xFFFFFFFF:
+        raise NetworkXNoPath("no path between sequences")
+    return (dist, info) if return_info else dist
+
+
+def sequence_nodes(path, seq_a, seq_b, *, directed: bool = True, raw_bytes_id: bool = False, device: int = 0):
+    """The reference's ``seq2nodes[seq_a]``, ``seq2nodes[seq_b]`` (analysis.py:96-108) without the
+    search (extension): the keys (``str``, or ``bytes`` with ``raw_bytes_id``) of the nodes that carry
+    each sequence, in node order.  Errors and warnings as ``sequence_distance``'s, up to the
+    KeyError."""
+    _dist, keys, _info = _seq_pass(path, seq_a, seq_b, directed, raw_bytes_id, False, device, "sequence_nodes")
+    return keys[0], keys[1]
 
 
 def _run(path, opts) -> RawResult:

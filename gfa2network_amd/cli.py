@@ -7,8 +7,8 @@ gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backen
 lines on the GPU from the same parse; ``stats`` (cli.py:152-159, 364-376) prints
 ``compute_stats``'s six numbers, taken on the GPU from the CSR; ``distance --path`` and
 ``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same CSR.
-Graph outputs (``--graph``, export graphml / gexf / json) and ``distance --seq`` (sequences stored
-on nodes) are outside the GPU GFA->CSR path.
+Graph outputs (``--graph``, export graphml / gexf / json) are outside the GPU GFA->CSR path;
+``distance --seq`` is served by the function ``sequence_distance`` and not routed here yet.
 """
 from __future__ import annotations
 
@@ -107,7 +107,7 @@ def main(argv: list[str] | None = None) -> None:
         return
     if args.cmd == "distance":  # cli.py:307-346
         if args.seq:
-            parser.error("distance --seq needs sequences stored on nodes, outside the GPU GFA->CSR path")
+            parser.error("distance --seq is not routed here yet: call gfa2network_amd.sequence_distance(GFA, A, B)")
         if args.backend == "igraph":
             parser.error("--backend igraph is outside the GPU GFA->CSR path")
         name_a, name_b = args.path

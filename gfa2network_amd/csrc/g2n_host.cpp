@@ -430,6 +430,69 @@ int g2n_distances_from_path(const char* path, const g2n_options* opts, const g2n
   return build_from_path(path, &o, res);
 }
 
+int g2n_seq_distance_from_path(const char* path, const g2n_options* opts, const uint8_t* seq_a, uint64_t len_a,
+                               const uint8_t* seq_b, uint64_t len_b, uint32_t* out_dist, g2n_seq_hits** hits,
+                               g2n_seq_info* info, int32_t* oriented, g2n_result** res) {
+  if (!res || !path || !out_dist || !hits || !info || !oriented) return G2N_E_ARG;
+  if ((len_a && !seq_a) || (len_b && !seq_b)) return G2N_E_ARG;
+  *res = nullptr;
+  *hits = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  std::memset(info, 0, sizeof(*info));
+  *out_dist = 0xFFFFFFFFu;
+  *oriented = 0;
+  g2n_options o;  // the plain graph's build, as g2n_distances_from_path's
+  g2n_options_init(&o);
+  o.directed = opts->directed != 0;
+  o.asymmetric = 1;
+  o.dtype = G2N_BOOL;
+  o.output = G2N_OUT_CSR;
+  o.want_node_names = 1;
+  o.device = opts->device;
+  o.unknown_warned = opts->unknown_warned;
+  o.test_flags = opts->test_flags;
+  std::unique_ptr<g2n_seq_hits> h;
+  rc = g2n::guarded([&]() -> int {
+    h.reset(new g2n_seq_hits());
+    return G2N_OK;
+  });
+  if (rc) return rc;
+  g2n::SeqRequest req{};
+  req.seq[0] = seq_a;
+  req.seq[1] = seq_b;
+  req.len[0] = len_a;
+  req.len[1] = len_b;
+  req.check_ascii = opts->want_node_names != 0;
+  req.names_if_high = !req.check_ascii && o.directed;
+  req.dist = out_dist;
+  req.hits = h.get();
+  req.info = info;
+  req.oriented = oriented;
+  struct Scope {
+    explicit Scope(const g2n::SeqRequest* r) { g2n::set_seq_request(r); }
+    ~Scope() { g2n::set_seq_request(nullptr); }
+  } scope(&req);
+  rc = build_from_path(path, &o, res);
+  *hits = h.release();
+  return rc;
+}
+
+void g2n_seq_hits_get(const g2n_seq_hits* h, const int64_t** ids_a, uint64_t* n_a, const int64_t** ids_b,
+                      uint64_t* n_b) {
+  if (ids_a) *ids_a = h->ids[0].data();
+  if (n_a) *n_a = h->ids[0].size();
+  if (ids_b) *ids_b = h->ids[1].data();
+  if (n_b) *n_b = h->ids[1].size();
+}
+
+void g2n_seq_hits_names(const g2n_seq_hits* h, const uint8_t** blob, const int64_t** offsets) {
+  if (blob) *blob = h->names.data();
+  if (offsets) *offsets = h->name_offs.data();
+}
+
+void g2n_seq_hits_free(g2n_seq_hits* h) { delete h; }
+
 int g2n_upload_file_range(const char* path, uint64_t offset, uint64_t len, void* d_dst, int32_t device) {
   if (!path || (len && !d_dst)) return G2N_E_ARG;
   return g2n::guarded([&]() -> int {

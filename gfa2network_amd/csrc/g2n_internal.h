@@ -19,6 +19,14 @@ struct g2n_paths {
   std::vector<uint8_t> bad_bytes;  // that name or step
 };
 
+// g2n_seq_distance_from_path's node lists: the ids of the nodes that carry each sequence, ascending,
+// and those nodes' keys (A's, then B's: key i is names[name_offs[i], name_offs[i + 1]))
+struct g2n_seq_hits {
+  std::vector<int64_t> ids[2];
+  std::vector<uint8_t> names;
+  std::vector<int64_t> name_offs{0};
+};
+
 namespace g2n {
 
 // the P / O records of len bytes of GFA text into *out (g2n_paths.cpp)
@@ -120,6 +128,22 @@ struct DistRequest {
   int64_t* missing_step;      // out: -1, or a source step that is no node (nothing was searched then)
 };
 void set_dist_request(const DistRequest* req);  // nullptr: none (thread-local)
+
+// g2n_seq_distance_from_path: the same, for the distance between two sequences.  The staged input
+// stays on the device next to the CSR and the names; the nodes whose sequence equals a query are
+// found in its S records there (g2n_seq.hip) and g2n_csr_path_distances runs on the two id lists.
+// Only the ids, one distance and the scalars come back.
+struct SeqRequest {
+  const uint8_t* seq[2];  // host: the two queries
+  uint64_t len[2];
+  bool check_ascii;       // as StatsRequest::check_ascii
+  bool names_if_high;     // as DistRequest::names_if_high
+  uint32_t* dist;         // out: the fewest hops from a node of A to a node of B; 0xFFFFFFFF: none reached, or a set is empty
+  g2n_seq_hits* hits;     // out: the two lists of node ids, ascending
+  g2n_seq_info* info;
+  int32_t* oriented;      // out: 1 when a node key ends in ":+" or ":-"
+};
+void set_seq_request(const SeqRequest* req);  // nullptr: none (thread-local)
 
 // Parallel multi-member gunzip.  Members are found by their header bytes and inflated
 // speculatively on host_threads() threads; the chain of members from byte 0 (zero padding

@@ -26,6 +26,7 @@
 #include "g2n_keyset.hip"
 #include "g2n_stats.hip"
 #include "g2n_dist.hip"
+#include "g2n_seq.hip"
 
 #define G2N_HIP(call)                                                                                      \
   do {                                                                                                     \
@@ -49,6 +50,7 @@ enum Slot {
   S_DSEEN, S_DNEXT, S_DQUEUE, S_DQMASK, S_DLONG, S_DSTATE, S_DCNT, S_DMPTR, S_DCUR, S_DMPATH, S_DSPATH, S_DDONE,
   S_DTAB, S_DPP, S_DPN,  // g2n_csr_path_distances (g2n_dist.hip)
   S_DFLAG, S_DKS, S_DSBLOB, S_DSOFFS, S_DIDS,  // g2n_distances_from_path: the step lookup
+  S_QSTATE, S_QLINES, S_QNODE, S_QFPOS, S_QFLAG, S_QLAST, S_QCAND, S_QIDS, S_QBYTES, S_QNLEN, S_QNOFF, S_QNBLOB,  // g2n_seq_distance_from_path (g2n_seq.hip)
   S_NSLOTS
 };
 
@@ -2586,6 +2588,8 @@ static thread_local const StatsRequest* t_stats_request = nullptr;
 void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
 static thread_local const DistRequest* t_dist_request = nullptr;
 void set_dist_request(const DistRequest* req) { t_dist_request = req; }
+static thread_local const SeqRequest* t_seq_request = nullptr;
+void set_seq_request(const SeqRequest* req) { t_seq_request = req; }
 
 // H's result as D's scalars, no matrix and no names (a stats or distance request's build)
 static void scalars_result(g2n_context* c, const g2n_result& D, HostResult* H) {
@@ -2728,12 +2732,198 @@ static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
+// A sequence-distance build's result (g2n_seq_distance_from_path): as dist_result up to the key
+// table; then the S records of the staged input in[0, len) give the two lists of node ids
+// (g2n_seq.hip), which g2n_csr_path_distances searches as K = 2.
+static void seq_result(g2n_context* c, const g2n_result& D, HostResult* H, const SeqRequest& q, const uint8_t* in,
+                       uint64_t len) {
+  scalars_result(c, D, H);
+  *q.oriented = 0;
+  *q.dist = kDistUnreached;
+  std::memset(q.info, 0, sizeof(*q.info));
+  *q.hits = g2n_seq_hits();
+  if (D.status != G2N_OK) return;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_seq_distance_from_path: the build returned no CSR");
+  const uint64_t n = (uint64_t)D.n_nodes;
+  if (n && (!D.names_blob || !D.names_offsets)) throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: no names");
+  if (q.check_ascii && ascii_key_check(c, D, H)) return;
+  if (q.names_if_high && n && D.names_bytes) {
+    StatsOut* so = stats_out_reset(c);
+    const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
+    hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
+    if (read_dev(c, so).high_off != ~0ull) {
+      g2n_result& R = H->r;
+      const int64_t* offs = (const int64_t*)download(c, H->offs, D.names_offsets, (size_t)(n + 1) * sizeof(int64_t));
+      G2N_HIP(hipStreamSynchronize(c->stream));
+      R.names_blob = (const uint8_t*)download(c, H->blob, D.names_blob, (size_t)offs[n]);
+      R.names_offsets = offs;
+      R.names_bytes = D.names_bytes;
+      G2N_HIP(hipStreamSynchronize(c->stream));
+    }
+  }
+  const uint64_t n_s = c->last_n_segs;
+  if (n_s >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_seq_distance_from_path: 2^32-1 or more S lines");
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (auto& x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  // ---- the line starts "S\t": the one pass over every byte
+  auto* st = dget<SeqState>(c, S_QSTATE, 1);
+  auto* lines = dget<uint64_t>(c, S_QLINES, n_s);
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(SeqState), c->stream));
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  if (len)
+    hipLaunchKernelGGL(k_seq_lines, dim3(std::min(grid_for((len + 15) / 16), gcap)), dim3(256), 0, c->stream, in, len,
+                       n_s, lines, st);
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  // ---- the orientation flag and the key table over the names' own blob (as dist_result)
+  auto* flag = dget<unsigned long long>(c, S_DFLAG, 2);
+  G2N_HIP(hipMemsetAsync(flag, 0, 16, c->stream));
+  if (n)
+    hipLaunchKernelGGL(k_key_oriented, dim3(std::min(grid_for(n), gcap)), dim3(256), 0, c->stream, D.names_blob,
+                       D.names_offsets, n, (uint32_t*)flag);
+  uint64_t cap = 1024;
+  while (cap < 2 * n) cap *= 2;
+  auto* table = dget<KsEntry>(c, S_DKS, cap);
+  G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(KsEntry), c->stream));
+  if (n)
+    hipLaunchKernelGGL(k_ks_insert, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, D.names_blob, D.names_offsets, n,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int64_t*)nullptr, (uint64_t)0,
+                       (uint64_t)0, table, cap - 1, (uint8_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr, 1);
+  if (read_dev(c, st).n_lines != n_s)
+    throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: the S lines found differ from the build's count");
+  // ---- the queries: one holding a tab or a newline equals no field; the bytes past the first 16
+  // are read on the device only by k_seq_compare
+  SeqQuery sq{};
+  uint64_t qoff[2] = {0, 0}, qbytes = 0;
+  for (int k = 0; k < 2; k++) {
+    const uint8_t* s = q.seq[k];
+    const uint64_t m = q.len[k];
+    const bool never = m && (std::memchr(s, '\t', m) || std::memchr(s, '\n', m));
+    sq.m[k] = never ? kSeqNoQuery : m;
+    if (never) continue;
+    if (m) std::memcpy(sq.head[k], s, (size_t)std::min<uint64_t>(m, kSeqHead));
+    if (m > kSeqHead) {
+      qoff[k] = qbytes;
+      qbytes += (m + 15) & ~15ull;
+    }
+  }
+  auto* dq = dget<uint8_t>(c, S_QBYTES, qbytes);
+  for (int k = 0; k < 2; k++)
+    if (sq.m[k] != kSeqNoQuery && sq.m[k] > kSeqHead)
+      G2N_HIP(hipMemcpyAsync(dq + qoff[k], q.seq[k], (size_t)sq.m[k], hipMemcpyHostToDevice, c->stream));
+  // ---- one lane per S line, the long candidates' remaining bytes, the node lists
+  auto* node_of = dget<uint32_t>(c, S_QNODE, n_s);
+  auto* fpos = dget<uint64_t>(c, S_QFPOS, n_s);
+  auto* flags = dget<uint32_t>(c, S_QFLAG, n_s);
+  auto* last = dget<unsigned long long>(c, S_QLAST, n);
+  auto* cand = dget<uint32_t>(c, S_QCAND, 2 * n_s);
+  auto* ids = dget<uint32_t>(c, S_QIDS, 2 * n_s);
+  G2N_HIP(hipMemsetAsync(last, 0, n * 8, c->stream));
+  SeqState h{};
+  if (n_s) {
+    hipLaunchKernelGGL(k_seq_classify, dim3(grid_for(n_s, 256)), dim3(256), 0, c->stream, in, len,
+                       (const uint64_t*)lines, n_s, (const KsEntry*)table, cap - 1, D.names_blob, n, sq, node_of, fpos,
+                       flags, last, cand, cand + n_s, st);
+    h = read_dev(c, st);
+    if (h.bad) throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: an S name is no node");
+    for (int k = 0; k < 2; k++)
+      if (sq.m[k] != kSeqNoQuery && sq.m[k] > kSeqHead && h.cand[k])
+        hipLaunchKernelGGL(k_seq_compare, dim3(std::min<unsigned>(h.cand[k], gcap)), dim3(256), 0, c->stream, in, len,
+                           (const uint8_t*)(dq + qoff[k]), sq.m[k], kSeqCand << k, (const uint32_t*)(cand + k * n_s),
+                           (uint64_t)h.cand[k], (const uint64_t*)fpos, flags);
+    hipLaunchKernelGGL(k_seq_nodes, dim3(grid_for(n_s, 256)), dim3(256), 0, c->stream, (const uint64_t*)lines, n_s,
+                       (const uint32_t*)node_of, (const uint32_t*)flags, (const unsigned long long*)last, ids, ids + n_s,
+                       st);
+    h = read_dev(c, st);
+  }
+  G2N_HIP(hipEventRecord(ev.e[2], c->stream));
+  unsigned long long oriented = 0;
+  G2N_HIP(hipMemcpyAsync(&oriented, flag, 8, hipMemcpyDeviceToHost, c->stream));
+  // ---- the two lists, ascending (the appends' order is arbitrary)
+  std::vector<uint32_t> got[2];
+  for (int k = 0; k < 2; k++) {
+    if (h.hits[k] > n_s) throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: node list overflow");
+    got[k].resize(h.hits[k]);
+    if (h.hits[k])
+      G2N_HIP(hipMemcpyAsync(got[k].data(), ids + k * n_s, (size_t)h.hits[k] * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *q.oriented = (uint32_t)oriented != 0;
+  std::vector<int64_t> pn;
+  for (int k = 0; k < 2; k++) {
+    std::sort(got[k].begin(), got[k].end());
+    q.hits->ids[k].assign(got[k].begin(), got[k].end());
+    pn.insert(pn.end(), got[k].begin(), got[k].end());
+  }
+  float ms_scan = 0.f, ms_match = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms_scan, ev.e[0], ev.e[1]));
+  G2N_HIP(hipEventElapsedTime(&ms_match, ev.e[1], ev.e[2]));
+  q.info->n_s_lines = (int64_t)n_s;
+  q.info->n_with_seq = (int64_t)h.n_with_seq;
+  q.info->candidates_a = (int64_t)h.cand[0];
+  q.info->candidates_b = (int64_t)h.cand[1];
+  q.info->ms_scan = ms_scan;
+  q.info->ms_match = ms_match;
+  // ---- the listed nodes' keys (A's, then B's)
+  const uint64_t T = pn.size();
+  auto* dpn = dget<int64_t>(c, S_DPN, T);
+  std::vector<int64_t>& noffs = q.hits->name_offs;
+  noffs.assign(T + 1, 0);
+  if (T) {
+    auto* dlens = dget<int64_t>(c, S_QNLEN, T);
+    auto* doffs = dget<int64_t>(c, S_QNOFF, T + 1);
+    G2N_HIP(hipMemcpyAsync(dpn, pn.data(), T * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_seq_hit_lens, dim3(grid_for(T, 256)), dim3(256), 0, c->stream, (const int64_t*)dpn, T, n,
+                       D.names_offsets, dlens);
+    G2N_HIP(hipMemcpyAsync(noffs.data() + 1, dlens, T * 8, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < T; i++) {
+      if (noffs[i + 1] < 0 || noffs[i + 1] > D.names_bytes)
+        throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: key length out of range");
+      noffs[i + 1] += noffs[i];
+    }
+    const uint64_t nbytes = (uint64_t)noffs[T];
+    auto* dblob = dget<uint8_t>(c, S_QNBLOB, nbytes);
+    q.hits->names.resize(nbytes);
+    G2N_HIP(hipMemcpyAsync(doffs, noffs.data(), (T + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_seq_hit_names, dim3(grid_for(T, 256)), dim3(256), 0, c->stream, (const int64_t*)dpn, T, n,
+                       D.names_offsets, D.names_blob, (const int64_t*)doffs, dblob);
+    if (nbytes) G2N_HIP(hipMemcpyAsync(q.hits->names.data(), dblob, nbytes, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+  }
+  if (got[0].empty() || got[1].empty()) return;  // nothing to search
+  // ---- the search: K = 2, cell [0][1]
+  const int64_t pp[3] = {0, (int64_t)got[0].size(), (int64_t)pn.size()};
+  auto* dpp = dget<int64_t>(c, S_DPP, 3);
+  auto* dtab = dget<uint32_t>(c, S_DTAB, 4);
+  G2N_HIP(hipMemcpyAsync(dpp, pp, sizeof(pp), hipMemcpyHostToDevice, c->stream));
+  g2n_dist_info di;
+  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, 2, G2N_DIST_MIN, dtab, &di);
+  uint32_t tab[4];
+  G2N_HIP(hipMemcpyAsync(tab, dtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *q.dist = tab[1];
+  q.info->levels = di.levels;
+  q.info->launches = di.launches;
+  q.info->batches = di.batches;
+  q.info->ms_bfs = di.ms_bfs;
+}
+
 // the outputs of one host build: the matrix and names, or (a stats / distance request) scalars
-static void host_result(g2n_context* c, const g2n_result& D, HostResult* H) {
+// (in: the len input bytes the build read, still staged on the device)
+static void host_result(g2n_context* c, const g2n_result& D, HostResult* H, const uint8_t* in, uint64_t len) {
   if (t_stats_request)
     stats_result(c, D, H, *t_stats_request);
   else if (t_dist_request)
     dist_result(c, D, H, *t_dist_request);
+  else if (t_seq_request)
+    seq_result(c, D, H, *t_seq_request, in, len);
   else
     download_result(c, D, H);
 }
@@ -2762,7 +2952,7 @@ int build_host_fill(size_t len, const FillFn& fill, const g2n_options* opts, g2n
   double t2 = now_ms();
   HostResult* H = new_host_result();
   try {
-    host_result(c, D, H);
+    host_result(c, D, H, din, len);
   } catch (...) {
     delete H;
     throw;
@@ -2809,7 +2999,7 @@ int build_host_bgzf(const uint8_t* z, size_t zlen, const std::vector<ZMember>& m
   const double t2 = now_ms();
   HostResult* H = new_host_result();
   try {
-    host_result(c, D, H);
+    host_result(c, D, H, din, total_out);
   } catch (...) {
     delete H;
     throw;

@@ -563,6 +563,40 @@ int g2n_csr_path_distances_host(const void *indptr, const void *indices, int32_t
                                 const int64_t *path_ptr, const int64_t *path_nodes, uint64_t K, int32_t mode,
                                 void *out_tables, int32_t device, g2n_dist_info *info);
 
+/* ---- sequence distance (gfa2network/analysis.py:68-113 sequence_distance, `distance --seq`) -----
+ * The fewest hops from any node whose sequence is seq_a to any node whose sequence is seq_b, over
+ * the plain graph g2n_distances_from_path builds (of opts only directed, want_node_names, device,
+ * unknown_warned and test_flags are read).  The input's bytes stay on the device after the build;
+ * the nodes that carry a sequence are found there from its S records (g2n_seq.hip), no sequence
+ * byte comes back to the host.  The sequence of an S record (parser.py:135-163): fields[2] when
+ * int(fields[2]) raises ValueError (b"" and b"*" are sequences), else fields[3] when it exists and
+ * is not tag-shaped (split(b":", 2) into parts of lengths 2, 1, any), else none; a line with fewer
+ * than three fields has none.  The sequence of a node (builders.py:164-189): that of the last S
+ * record of its name, in file order, that has one.  A query holding '\t' or '\n' matches nothing.
+ * *out_dist = 0xFFFFFFFF when no node of B is reached or either set is empty (nothing is searched
+ * then; the reference's KeyError is the caller's to raise from the empty list).  *hits: the two
+ * node-id lists, ascending = node order, to be freed with g2n_seq_hits_free; the pointers of
+ * g2n_seq_hits_get live until then.  info: n_s_lines = the S records, n_with_seq = those that have
+ * a sequence, candidates_* = the records whose sequence field ends where the query would and
+ * starts with its first min(len, 16) bytes (only these are compared further); levels / launches /
+ * batches as g2n_dist_info's; ms_scan = the pass over the input's bytes, ms_match = the key table,
+ * the per-record pass, the comparisons and the node lists, ms_bfs = the search (hipEvent, pipeline
+ * stream).  *oriented and *res as g2n_distances_from_path's. */
+typedef struct g2n_seq_info {
+  int64_t n_s_lines, n_with_seq, candidates_a, candidates_b;
+  int64_t levels, launches, batches;
+  double ms_scan, ms_match, ms_bfs;
+} g2n_seq_info;
+typedef struct g2n_seq_hits g2n_seq_hits;
+int g2n_seq_distance_from_path(const char *path, const g2n_options *opts, const uint8_t *seq_a, uint64_t len_a,
+                               const uint8_t *seq_b, uint64_t len_b, uint32_t *out_dist, g2n_seq_hits **hits,
+                               g2n_seq_info *info, int32_t *oriented, g2n_result **res);
+void g2n_seq_hits_get(const g2n_seq_hits *h, const int64_t **ids_a, uint64_t *n_a, const int64_t **ids_b,
+                      uint64_t *n_b);
+/* the listed nodes' keys, A's then B's: key i is blob[offsets[i] .. offsets[i + 1]), n_a + n_b + 1 offsets */
+void g2n_seq_hits_names(const g2n_seq_hits *h, const uint8_t **blob, const int64_t **offsets);
+void g2n_seq_hits_free(g2n_seq_hits *h);
+
 #ifdef __cplusplus
 }
 #endif
