@@ -3818,8 +3818,8 @@ __global__ void __launch_bounds__(kTPB) k_first_of(uint64_t n_nodes, const uint3
   if (d < n_nodes) out[d] = inv ? inv[d] : (uint32_t)d;
 }
 
-// owner rank of a key: FNV-1a of its bytes mod n_ranks (any fixed function of the bytes works:
-// equal keys must meet on one rank)
+// owner rank of a key: fmix64(FNV-1a 64 of its bytes) mod n_ranks (any fixed function of the bytes
+// works: equal keys must meet on one rank; this one is pinned by tests/test_gpu_shard_primitives.py)
 __global__ void __launch_bounds__(kTPB) k_key_owner(const uint8_t* __restrict__ blob,
                                                     const int64_t* __restrict__ offs, uint64_t n, uint32_t n_ranks,
                                                     uint32_t* __restrict__ owner, uint32_t* __restrict__ idx) {

@@ -357,9 +357,11 @@ int g2n_keyset_view(g2n_keyset *ks, const uint8_t **d_blob, const int64_t **d_of
                     uint64_t *blob_len);
 void g2n_keyset_free(g2n_keyset *ks);
 
-/* Key i of the names blob goes to rank (FNV-1a of its bytes) mod n_ranks: the keys, grouped
- * by rank (order kept within a rank), to d_out_blob / d_out_offsets (n + 1); d_out_index[j] =
- * the input index of output key j; d_starts[r] = first output key of rank r. */
+/* Key i of the names blob goes to rank fmix64(FNV-1a 64 of its bytes) mod n_ranks (fmix64:
+ * MurmurHash3's 64-bit finaliser; 1 <= n_ranks <= 4096, else G2N_E_ARG) — every rank of a group,
+ * on whichever GPU, computes the same owner: the keys, grouped by rank (order kept within a rank),
+ * to d_out_blob / d_out_offsets (n + 1); d_out_index[j] = the input index of output key j;
+ * d_starts[r] = first output key of rank r (d_starts[n_ranks] = n). */
 int g2n_partition_keys(g2n_context *ctx, const uint8_t *d_blob, uint64_t blob_len, const int64_t *d_offsets,
                        uint64_t n, uint32_t n_ranks, uint8_t *d_out_blob, int64_t *d_out_offsets,
                        uint32_t *d_out_index, uint32_t *d_starts);
