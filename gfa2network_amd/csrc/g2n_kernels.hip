@@ -3179,7 +3179,7 @@ struct Acc<double> {
 template <class T>
 __device__ inline bool exact_term(T v) {
   double d = (double)v;
-  return d == __builtin_trunc(d);  // integral (false for inf/nan)
+  return d == __builtin_trunc(d);  // integral (false for nan; inf counts, and fails the sum |x| bound)
 }
 
 
@@ -3503,9 +3503,11 @@ __device__ inline uint32_t row_sum_one(uint32_t len, At at, Put put, void* scr_a
       T x = a[q].v;
       bool exact = true;
       double sabs = 0.0;
+      uint32_t nans = 0;
       if (Acc<T>::is_float()) {
         exact = exact_term(x);
         sabs = __builtin_fabs((double)x);
+        nans = x != x;
       }
       q++;
       while (q < len && a[q].c == c) {
@@ -3513,13 +3515,16 @@ __device__ inline uint32_t row_sum_one(uint32_t len, At at, Put put, void* scr_a
         if (Acc<T>::is_float()) {
           exact = exact && exact_term(y);
           sabs += __builtin_fabs((double)y);
+          nans += y != y;
         }
         x = Acc<T>::add(x, y);
         q++;
       }
       // a group of >= 3 terms whose sum depends on their order (std::sort on > 16 elements is
-      // not an insertion sort, so scipy's order is not the stable one)
-      if (Acc<T>::is_float() && q - q0 >= 3 && !(exact && sabs < Acc<T>::limit())) flag = true;
+      // not an insertion sort, so scipy's order is not the stable one), or one that holds two NaNs:
+      // x86 keeps the first NaN operand's payload and sign, so even a pair's sum follows the order
+      if (Acc<T>::is_float() && ((q - q0 >= 3 && !(exact && sabs < Acc<T>::limit())) || nans >= 2))
+        flag = true;
       put(u++, c, x);
     }
   }
