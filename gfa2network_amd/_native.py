@@ -42,7 +42,7 @@ EXPORTED = [
     "g2n_gunzip", "g2n_gunzip_chunked", "g2n_free", "g2n_split_render", "g2n_split_get", "g2n_split_segments", "g2n_split_free", "g2n_join_names", "g2n_gather_names", "g2n_write_npz", "g2n_write_node_map", "g2n_first_bad_utf8",
     "g2n_csr_stats", "g2n_csr_stats_host", "g2n_stats_from_path",
     "g2n_csr_path_distances", "g2n_csr_path_distances_host", "g2n_load_paths", "g2n_paths_get", "g2n_paths_free",
-    "g2n_distances_from_path",
+    "g2n_distances_from_path", "g2n_csr_path_distances_weighted", "g2n_csr_path_distances_weighted_host",
     "g2n_seq_distance_from_path", "g2n_seq_hits_get", "g2n_seq_hits_names", "g2n_seq_hits_free",
 ]
 
@@ -160,6 +160,19 @@ class DistInfo(ctypes.Structure):
         ("batches", ctypes.c_int64),
         ("ms_resolve", ctypes.c_double),
         ("ms_bfs", ctypes.c_double),
+    ]
+
+
+class WDistInfo(ctypes.Structure):
+    """g2n_wdist_info (include/g2n.h)."""
+
+    _fields_ = [
+        ("rounds", ctypes.c_int64),
+        ("launches", ctypes.c_int64),
+        ("batches", ctypes.c_int64),
+        ("batch_paths", ctypes.c_int64),
+        ("ms_search", ctypes.c_double),
+        ("ms_tables", ctypes.c_double),
     ]
 
 
@@ -348,6 +361,12 @@ def load() -> ctypes.CDLL:
     lib.g2n_csr_path_distances.restype = ctypes.c_int
     lib.g2n_csr_path_distances_host.argtypes = [P, P, I32, U64, U64, P, P, U64, I32, P, I32, ctypes.POINTER(DistInfo)]
     lib.g2n_csr_path_distances_host.restype = ctypes.c_int
+    lib.g2n_csr_path_distances_weighted.argtypes = [P, P, P, I32, P, U64, U64, P, P, U64, I32, P,
+                                                    ctypes.POINTER(WDistInfo)]
+    lib.g2n_csr_path_distances_weighted.restype = ctypes.c_int
+    lib.g2n_csr_path_distances_weighted_host.argtypes = [P, P, I32, P, U64, U64, P, P, U64, I32, P, I32,
+                                                         ctypes.POINTER(WDistInfo)]
+    lib.g2n_csr_path_distances_weighted_host.restype = ctypes.c_int
     lib.g2n_load_paths.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.g2n_load_paths.restype = ctypes.c_int
     lib.g2n_paths_get.argtypes = [P] + [P] * 9
@@ -595,6 +614,48 @@ def csr_path_distances_host(indptr: np.ndarray, indices: np.ndarray, n: int, pat
         raise RuntimeError(f"{status_name(rc)}: {last_error()}")
     return tuple(out), {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
                         "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
+
+
+def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, values: np.ndarray, n: int,
+                                     path_ptr: np.ndarray, path_nodes: np.ndarray, mean: bool,
+                                     device: int = 0) -> tuple[tuple, dict]:
+    """g2n_csr_path_distances_weighted_host on a host CSR (indptr / indices both int32 or both int64,
+    float64 values) and K paths (as csr_path_distances_host): ((D,) or (S, C), the g2n_wdist_info
+    fields) — the directed K x K tables, float64 D (inf = unreached) or float64 S and uint64 C."""
+    lib = load()
+    idt = np.dtype(indptr.dtype)
+    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
+        raise TypeError("indptr / indices must both be int32 or both int64")
+    if np.dtype(values.dtype) != np.dtype(np.float64):
+        raise TypeError("values must be float64")
+    ip, ix, val = np.ascontiguousarray(indptr), np.ascontiguousarray(indices), np.ascontiguousarray(values)
+    pp = np.ascontiguousarray(path_ptr, dtype=np.int64)
+    pn = np.ascontiguousarray(path_nodes, dtype=np.int64)
+    if len(ip) != n + 1:
+        raise ValueError("indptr must hold n + 1 offsets")
+    if len(val) != len(ix):
+        raise ValueError("values must hold one value per index")
+    K = len(pp) - 1
+    if K < 0 or pp[0] != 0 or pp[K] != len(pn):
+        raise ValueError("path_ptr must hold K + 1 offsets from 0 to len(path_nodes)")
+    out = np.empty((2 if mean else 1, K, K), dtype=np.float64)
+    info = WDistInfo()
+    rc = lib.g2n_csr_path_distances_weighted_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize,
+                                                  val.ctypes.data if val.size else None, n, len(ix), pp.ctypes.data,
+                                                  pn.ctypes.data if pn.size else None, K,
+                                                  DIST_MEAN if mean else DIST_MIN,
+                                                  out.ctypes.data if out.size else None, int(device),
+                                                  ctypes.byref(info))
+    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
+        raise NotImplementedError(f"GPU weighted path distances: {last_error()}")
+    if rc == E_ARG:
+        raise ValueError(f"GPU weighted path distances: {last_error()}")
+    if rc != OK:
+        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+    tabs = (out[0], out[1].view(np.uint64)) if mean else (out[0],)
+    return tabs, {"rounds": int(info.rounds), "launches": int(info.launches), "batches": int(info.batches),
+                  "batch_paths": int(info.batch_paths), "ms_search": float(info.ms_search),
+                  "ms_tables": float(info.ms_tables)}
 
 
 class Paths:

@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "load_paths", "genome_distance", "genome_distance_matrix",
+           "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "load_paths", "genome_distance", "genome_distance_matrix",
            "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
@@ -797,8 +797,75 @@ def mean_table(S: np.ndarray, C: np.ndarray) -> np.ndarray:
     return M
 
 
-def path_distances(A, paths, *, method: str = "min", device: int = 0, return_info: bool = False):
-    """Hop distances between node lists over the graph whose adjacency structure is the square scipy
+def weighted_min_table(D: np.ndarray) -> np.ndarray:
+    """The directed float64 table of g2n_csr_path_distances_weighted's ``D`` (already float64, ``inf``
+    where no step is reached) with 0.0 on the diagonal."""
+    M = np.array(D, dtype=np.float64)
+    np.fill_diagonal(M, 0.0)
+    return M
+
+
+def weighted_mean_table(S: np.ndarray, C: np.ndarray) -> np.ndarray:
+    """The symmetric mean from g2n_csr_path_distances_weighted's directed float64 sums ``S`` and uint64
+    counts ``C``: ``(S[i][j] + S[j][i]) / float(C[i][j] + C[j][i])`` — one addition and one division
+    in float64 —, ``inf`` where nothing is reached, 0.0 on the diagonal."""
+    S, C = np.asarray(S, dtype=np.float64), np.asarray(C, dtype=np.uint64)
+    den = C + C.T
+    M = np.full(S.shape, np.inf, dtype=np.float64)
+    np.divide(S + S.T, den.astype(np.float64), out=M, where=den > 0)
+    np.fill_diagonal(M, 0.0)
+    return M
+
+
+def _weighted_csr(A):
+    """``A`` as a CSR whose data is float64, every value finite and >= 0 (checked here, on the host):
+    a CSR keeps its entries as they are stored (repeated ones are parallel edges), another format goes
+    through scipy's own ``tocsr()``."""
+    if np.issubdtype(A.dtype, np.complexfloating):
+        raise TypeError("path_distances(weighted=True) takes real edge lengths, not a complex matrix")
+    if A.format != "csr":
+        A = A.tocsr()
+    data = np.ascontiguousarray(A.data, dtype=np.float64)
+    if data.size and not (np.isfinite(data).all() and (data >= 0).all()):
+        raise ValueError("path_distances(weighted=True) takes finite edge lengths >= 0")
+    return A, data
+
+
+def _path_arrays(paths):
+    lists = [np.asarray(p, dtype=np.int64).reshape(-1) for p in paths]
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(p) for p in lists], out=ptr[1:])
+    return ptr, np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+
+
+def _weighted_path_distances(A, paths, method, device, return_info):
+    A, data = _weighted_csr(A)
+    n = int(A.shape[0])
+    if n >= 2**31 - 1:
+        raise NotImplementedError("GPU path distances need node ids below 2^31 - 1")
+    ptr, nodes = _path_arrays(paths)
+    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
+    mean = method != "min"
+    tabs, info = nat.csr_path_distances_weighted_host(np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt),
+                                                      data, n, ptr, nodes, mean, device)
+    M = weighted_mean_table(*tabs) if mean else weighted_min_table(tabs[0])
+    return (M, info) if return_info else M
+
+
+def path_distances(A, paths, *, method: str = "min", weighted: bool = False, device: int = 0,
+                   return_info: bool = False):
+    """``weighted=False`` (the default) — hop distances, as described below.  ``weighted=True`` — the
+    stored values are edge lengths: ``A.data`` is taken as float64 (bool, integer and float32 values
+    convert exactly; a complex matrix raises TypeError), every value must be finite and >= 0
+    (ValueError otherwise, before the GPU is touched), an explicit zero is an edge of length 0 and
+    the repeated entries of a non-canonical CSR are parallel edges; a matrix that is not CSR goes
+    through ``A.tocsr()``.  The distances are those of NetworkX's ``multi_source_dijkstra_path_length
+    (G, nodes, weight="weight")`` / scipy's ``dijkstra``, bit for bit (g2n_wdist.hip): ``min`` is the
+    directed float64 table, any other method ``(S[i][j] + S[j][i]) / float(C[i][j] + C[j][i])`` with
+    ``S`` summed in step order; ``return_info=True`` then returns the g2n_wdist_info fields (rounds,
+    launches, batches, batch_paths, ms_*).
+
+    Hop distances between node lists over the graph whose adjacency structure is the square scipy
     sparse matrix ``A`` (extension; the counterpart of ``graph_stats``): every stored (u, v) is an
     edge u -> v of weight 1, the values are never read.  ``paths`` is a list of lists of node
     indices, duplicates kept.  ``method="min"`` returns the directed K x K float64 table
@@ -811,6 +878,8 @@ def path_distances(A, paths, *, method: str = "min", device: int = 0, return_inf
         raise TypeError("path_distances takes a scipy sparse matrix")
     if A.shape[0] != A.shape[1]:
         raise ValueError("path_distances takes a square matrix")
+    if weighted:
+        return _weighted_path_distances(A, paths, method, device, return_info)
     if A.format != "csr":
         # structure only: unit values in a dtype whose sums cannot overflow
         C = A.tocoo()

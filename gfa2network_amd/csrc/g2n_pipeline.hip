@@ -26,6 +26,7 @@
 #include "g2n_keyset.hip"
 #include "g2n_stats.hip"
 #include "g2n_dist.hip"
+#include "g2n_wdist.hip"
 #include "g2n_seq.hip"
 
 #define G2N_HIP(call)                                                                                      \
@@ -49,6 +50,7 @@ enum Slot {
   S_STPARENT, S_STCOL, S_STDIAG, S_STLONG, S_STOUT, S_STIP, S_STIX,  // g2n_csr_stats (g2n_stats.hip)
   S_DSEEN, S_DNEXT, S_DQUEUE, S_DQMASK, S_DLONG, S_DSTATE, S_DCNT, S_DMPTR, S_DCUR, S_DMPATH, S_DSPATH, S_DDONE,
   S_DTAB, S_DPP, S_DPN,  // g2n_csr_path_distances (g2n_dist.hip)
+  S_WDIST, S_WVAL,  // g2n_csr_path_distances_weighted (g2n_wdist.hip)
   S_DFLAG, S_DKS, S_DSBLOB, S_DSOFFS, S_DIDS,  // g2n_distances_from_path: the step lookup
   S_QSTATE, S_QLINES, S_QNODE, S_QFPOS, S_QFLAG, S_QLAST, S_QCAND, S_QIDS, S_QBYTES, S_QNLEN, S_QNOFF, S_QNBLOB,  // g2n_seq_distance_from_path (g2n_seq.hip)
   S_NSLOTS
@@ -2584,6 +2586,239 @@ int csr_path_distances_host(const void* indptr, const void* indices, int32_t ind
   return G2N_OK;
 }
 
+// ------------------------------------------------ weighted path distances ------
+// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
+// tables: device.  Nothing is written to the tables before every array has passed its check.
+template <class I>
+static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
+                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
+                              uint64_t steps, bool mean, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
+  const char* who = "g2n_csr_path_distances_weighted";
+  auto* st = dget<DistState>(c, S_DSTATE, 1);
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  // ---- the caller's arrays, checked whole; the steps' paths
+  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
+  G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
+                     indices, n, nnz, st);
+  if (nnz)
+    hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for(nnz), gcap)), dim3(256), 0, c->stream, values, nnz, st);
+  hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
+  if (steps)
+    hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
+                       step_path, cnt, st);
+  if (read_dev(c, st).bad)
+    throw Failure(G2N_E_ARG, std::string(who) + ": indptr / indices / path_ptr / path_nodes out of range, or a value "
+                                                "that is negative or not finite");
+  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
+  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
+  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
+  // ---- B paths a batch: B * n distances must fit what is free (and what the slot already holds)
+  uint64_t B = std::min<uint64_t>(64, K);
+  if (n) {
+    size_t f = 0, t = 0;
+    G2N_HIP(hipMemGetInfo(&f, &t));
+    const uint64_t avail = (uint64_t)f + c->bufs[S_WDIST].cap;
+    B = std::min<uint64_t>(B, avail / 10 * 8 / (n * 8));  // (the arena adds an eighth to what it is asked for)
+    if (B == 0)
+      throw Failure(G2N_E_UNSUPPORTED, std::string(who) + ": the distances of one path over " + std::to_string(n) +
+                                           " nodes exceed the device's free memory");
+  }
+  auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
+  info->batch_paths = (int64_t)B;
+  // ---- tables
+  auto* D = (unsigned long long*)tables;
+  if (!mean)
+    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(K * K), gcap)), dim3(256), 0, c->stream, D, K * K,
+                       kWDistInf);
+  std::vector<int64_t> h_ptr(K + 1);
+  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  const unsigned gn = std::min(grid_for(n), gcap);
+  int64_t launches = 0, rounds = 0, batches = 0;
+  double ms_search = 0.0, ms_tables = 0.0;
+  for (uint64_t base = 0; base < K; base += B, batches++) {
+    const uint64_t nb = std::min<uint64_t>(B, K - base);
+    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[base + nb];
+    if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
+    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(n * B), gcap)), dim3(256), 0, c->stream, dist, n * B,
+                       kWDistInf);
+    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+    launches++;
+    if (s1 > s0) {
+      hipLaunchKernelGGL(k_wdist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
+                         (const uint32_t*)step_path, (uint32_t)base, (uint32_t)B, dist, next);
+      launches++;
+    }
+    // round R expands the nodes that round R - 1 improved; the last one that improves anything is
+    // at most n - 1 (g2n_wdist.hip), so a frontier of a round past n is a failure, not a reason to go on
+    uint64_t R = 0;
+    for (bool more = s1 > s0; more;) {
+      if (R > n) throw Failure(G2N_E_DEVICE, std::string(who) + ": did not converge in n rounds");
+      // wide: round R's frontier from next (count, n_long, pending cleared first)
+      G2N_HIP(hipMemsetAsync(st, 0, 3 * sizeof(uint32_t), c->stream));
+      hipLaunchKernelGGL(k_wdist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, (uint32_t)R, queue, qmask, st);
+      launches++;
+      DistState h = read_dev(c, st);
+      if (h.count == 0) break;
+      if (h.count > kDistNarrowCap) {
+        hipLaunchKernelGGL(k_wdist_expand<I>, dim3(std::min(grid_for(h.count), gcap)), dim3(256), 0, c->stream, indptr,
+                           indices, values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
+                           (const unsigned long long*)qmask, long_rows, long_cap, st);
+        hipLaunchKernelGGL(k_wdist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices,
+                           values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
+                           (const unsigned long long*)qmask, (const uint32_t*)long_rows, long_cap, st);
+        launches += 2;
+        R++;
+        continue;
+      }
+      // narrow: one workgroup carries it until it empties, overflows or has run its budget
+      for (;;) {
+        const uint32_t budget = (uint32_t)std::min<uint64_t>(kWDistRoundBudget, n + 1 - R);  // (R <= n: >= 1)
+        hipLaunchKernelGGL(k_wdist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, values, n,
+                           nnz, (uint32_t)B, dist, next, queue, qmask, st, budget);
+        launches++;
+        h = read_dev(c, st);
+        if (h.level <= R || h.level > R + budget) throw Failure(G2N_E_DEVICE, std::string(who) + ": frontier state");
+        R = h.level;
+        if (h.pending) break;
+        if (h.count == 0) {
+          more = false;
+          break;
+        }
+        if (h.count > kDistNarrowCap) throw Failure(G2N_E_DEVICE, std::string(who) + ": frontier state");
+        if (R > n) throw Failure(G2N_E_DEVICE, std::string(who) + ": did not converge in n rounds");
+      }
+    }
+    const DistState h = read_dev(c, st);
+    if (h.bad) throw Failure(G2N_E_ARG, std::string(who) + ": indptr / indices out of range");
+    rounds = std::max<int64_t>(rounds, h.last_level);
+    // ---- the batch's rows of the tables
+    G2N_HIP(hipEventRecord(ev[1], c->stream));
+    if (mean)
+      hipLaunchKernelGGL(k_wdist_mean, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes, steps, n,
+                         K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base, (double*)tables,
+                         D + K * K);
+    else if (steps)
+      hipLaunchKernelGGL(k_wdist_min, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
+                         (const uint32_t*)step_path, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb,
+                         (uint32_t)base, D);
+    launches++;
+    G2N_HIP(hipEventRecord(ev[2], c->stream));
+    G2N_HIP(hipEventSynchronize(ev[2]));
+    float ms = 0.f;
+    G2N_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    ms_search += ms;
+    G2N_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    ms_tables += ms;
+  }
+  info->rounds = rounds;
+  info->launches = launches;
+  info->batches = batches;
+  info->ms_search = ms_search;
+  info->ms_tables = ms_tables;
+}
+
+static void wpath_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width,
+                            const double* values, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
+                            const int64_t* path_nodes, uint64_t K, int32_t mode, void* tables, g2n_wdist_info* info) {
+  const std::string who = "g2n_csr_path_distances_weighted";
+  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, who + ": index_width must be 4 or 8");
+  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, who + ": unknown mode");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more entries");
+  std::memset(info, 0, sizeof(*info));
+  info->batch_paths = (int64_t)std::max<uint64_t>(1, std::min<uint64_t>(64, K));
+  if (K == 0) return;
+  if (!path_ptr || !tables) throw Failure(G2N_E_ARG, who + ": null array");
+  if ((n && !indptr) || (nnz && (!indices || !values))) throw Failure(G2N_E_ARG, who + ": null array");
+  if (n == 0 && nnz) throw Failure(G2N_E_ARG, who + ": entries without rows");
+  int64_t ends[2];
+  G2N_HIP(hipMemcpyAsync(&ends[0], path_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipMemcpyAsync(&ends[1], path_ptr + K, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  if (ends[0] != 0 || ends[1] < 0) throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
+  const uint64_t steps = (uint64_t)ends[1];
+  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
+  if (steps && !path_nodes) throw Failure(G2N_E_ARG, who + ": null array");
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (auto& x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
+  if (index_width == 4)
+    wpath_distances_t<int32_t>(c, (const int32_t*)indptr, (const int32_t*)indices, values, n, nnz, path_ptr, path_nodes,
+                               K, steps, mode == G2N_DIST_MEAN, tables, info, ev.e);
+  else
+    wpath_distances_t<int64_t>(c, (const int64_t*)indptr, (const int64_t*)indices, values, n, nnz, path_ptr, path_nodes,
+                               K, steps, mode == G2N_DIST_MEAN, tables, info, ev.e);
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// bytes of the weighted tables of K paths (mean: S float64 then C uint64; min: D float64); 0 = past 2^63
+static uint64_t wdist_table_bytes(uint64_t K, int32_t mode) {
+  if (K >= (1ull << 29)) return 0;
+  return K * K * (mode == G2N_DIST_MEAN ? 16 : 8);
+}
+
+static void wdist_check_k(uint64_t K, int32_t mode) {
+  size_t f = 0, t = 0;
+  G2N_HIP(hipMemGetInfo(&f, &t));
+  const uint64_t want = wdist_table_bytes(K, mode);
+  if ((K && !want) || want + K * 8 > f)
+    throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_weighted: the K x K tables of " + std::to_string(K) +
+                                         " paths exceed the device's free memory");
+}
+
+int csr_path_distances_weighted_host(const void* indptr, const void* indices, int32_t index_width, const double* values,
+                                     uint64_t n, uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes,
+                                     uint64_t K, int32_t mode, void* out_tables, int32_t device, g2n_wdist_info* info) {
+  const std::string who = "g2n_csr_path_distances_weighted_host";
+  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, who + ": index_width must be 4 or 8");
+  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, who + ": unknown mode");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more entries");
+  if (!indptr || (nnz && (!indices || !values)) || !path_ptr || (K && !out_tables))
+    throw Failure(G2N_E_ARG, who + ": null array");
+  if (path_ptr[0] != 0 || path_ptr[K] < 0 || (path_ptr[K] && !path_nodes))
+    throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
+  const uint64_t steps = (uint64_t)path_ptr[K];
+  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
+  g2n_context* c = shared_context(device);
+  std::lock_guard<std::mutex> lk(c->mu);
+  enter_call(c);
+  G2N_HIP(hipSetDevice(c->device));
+  clear_call_state(c);
+  wdist_check_k(K, mode);
+  const size_t w = (size_t)index_width;
+  void* dip = dbuf(c, S_STIP, (size_t)(n + 1) * w);
+  void* dix = dbuf(c, S_STIX, (size_t)nnz * w);
+  auto* dval = dget<double>(c, S_WVAL, nnz);
+  auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
+  auto* dpn = dget<int64_t>(c, S_DPN, steps);
+  const uint64_t tbytes = wdist_table_bytes(K, mode);
+  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
+  G2N_HIP(hipMemcpyAsync(dip, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
+  if (nnz) G2N_HIP(hipMemcpyAsync(dix, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
+  if (nnz) G2N_HIP(hipMemcpyAsync(dval, values, (size_t)nnz * 8, hipMemcpyHostToDevice, c->stream));
+  G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
+  wpath_distances(c, dip, dix, index_width, dval, n, nnz, dpp, dpn, K, mode, dtab, info);
+  if (tbytes) G2N_HIP(hipMemcpyAsync(out_tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  shrink_shared(c);
+  return G2N_OK;
+}
+
 static thread_local const StatsRequest* t_stats_request = nullptr;
 void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
 static thread_local const DistRequest* t_dist_request = nullptr;
@@ -3849,6 +4084,30 @@ int g2n_csr_path_distances_host(const void* indptr, const void* indices, int32_t
   return g2n::guarded([&] {
     return g2n::csr_path_distances_host(indptr, indices, index_width, n, nnz, path_ptr, path_nodes, K, mode, out_tables,
                                         device, info);
+  });
+}
+
+int g2n_csr_path_distances_weighted(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width,
+                                    const double* d_values, uint64_t n, uint64_t nnz, const int64_t* d_path_ptr,
+                                    const int64_t* d_path_nodes, uint64_t K, int32_t mode, void* d_out_tables,
+                                    g2n_wdist_info* info) {
+  if (!info) return G2N_E_ARG;
+  G2N_CTX_CALL(ctx, {
+    g2n::wdist_check_k(K, mode);
+    g2n::wpath_distances(ctx, d_indptr, d_indices, index_width, d_values, n, nnz, d_path_ptr, d_path_nodes, K, mode,
+                         d_out_tables, info);
+  });
+  return G2N_OK;
+}
+
+int g2n_csr_path_distances_weighted_host(const void* indptr, const void* indices, int32_t index_width,
+                                         const double* values, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
+                                         const int64_t* path_nodes, uint64_t K, int32_t mode, void* out_tables,
+                                         int32_t device, g2n_wdist_info* info) {
+  if (!info) return G2N_E_ARG;
+  return g2n::guarded([&] {
+    return g2n::csr_path_distances_weighted_host(indptr, indices, index_width, values, n, nnz, path_ptr, path_nodes, K,
+                                                 mode, out_tables, device, info);
   });
 }
 

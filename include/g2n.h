@@ -565,6 +565,49 @@ int g2n_csr_path_distances_host(const void *indptr, const void *indices, int32_t
                                 const int64_t *path_ptr, const int64_t *path_nodes, uint64_t K, int32_t mode,
                                 void *out_tables, int32_t device, g2n_dist_info *info);
 
+/* ---- weighted path distances (a graph built with weight_tag: NetworkX's multi-source Dijkstra with
+ * weight="weight") -------------------------------------------------------------------------------
+ * Shortest-path distances between K node lists over a CSR with float64 values: every stored entry
+ * k of row u is an edge u -> indices[k] of length values[k]; repeated (u, v) are parallel edges, an
+ * explicit zero is an edge of length 0 (scipy.sparse.csgraph's reading).  Every value must be
+ * finite and >= 0 (-0.0 is 0): they are checked in one pass before anything is searched.  Paths as
+ * in g2n_csr_path_distances.  d_i(v) = the smallest left-to-right float64 sum ((0.0 + w1) + w2) +
+ * ... over the walks from a step of path i to v: 0.0 on its own steps, +inf when v is not reached
+ * (or every sum overflows) — bit for bit what Dijkstra returns (g2n_wdist.hip).  The tables are
+ * row-major K x K:
+ *   G2N_DIST_MIN   D, float64: D[i][j] = min over the steps v of j of d_i(v); +inf = none reached
+ *   G2N_DIST_MEAN  S float64, then C uint64: S[i][j] = the sum of d_i(v) over the steps v of j that
+ *                  i reaches, added in step order, left to right from 0.0, each occurrence counted
+ *                  (the same bits on every run); C[i][j] = how many those are
+ * info: rounds = the relaxation rounds of the longest batch (the last round that improved a
+ * distance; at most n - 1), launches = kernels launched, batch_paths = B <= 64, the paths searched
+ * together (B * n * 8 bytes of distances must fit the device's free memory), batches = ceil(K / B);
+ * ms_search = the checks and the searches, ms_tables = the tables (hipEvent, pipeline stream). */
+typedef struct g2n_wdist_info {
+  int64_t rounds, launches, batches, batch_paths;
+  double ms_search, ms_tables; /* hipEvent, pipeline stream */
+} g2n_wdist_info;
+
+/* DEVICE pointers on ctx's device (index_width 4 or 8 bytes per indptr / indices element, d_values
+ * float64, path arrays int64; a step of -1 is no node); d_out_tables holds K * K * 8 (min) or
+ * K * K * 16 (mean) bytes and is not written unless every array passed its check; scratch from
+ * ctx's arena; returns after the stream drained.  G2N_E_UNSUPPORTED for n >= 2^31 - 1, nnz >=
+ * 2^32 - 1, 2^32 - 1 or more steps, tables of K paths or one path's n distances past the device's
+ * free memory; G2N_E_ARG as g2n_csr_path_distances, and for a value that is negative, NaN or
+ * infinite (nothing out of range is ever addressed); G2N_E_DEVICE should a search not converge in
+ * n rounds (it cannot: the loop is bounded rather than trusted). */
+int g2n_csr_path_distances_weighted(g2n_context *ctx, const void *d_indptr, const void *d_indices, int32_t index_width,
+                                    const double *d_values, uint64_t n, uint64_t nnz, const int64_t *d_path_ptr,
+                                    const int64_t *d_path_nodes, uint64_t K, int32_t mode, void *d_out_tables,
+                                    g2n_wdist_info *info);
+
+/* The same for arrays in HOST memory (out_tables too): uploaded to `device` (the host entry
+ * points' cached context). */
+int g2n_csr_path_distances_weighted_host(const void *indptr, const void *indices, int32_t index_width,
+                                         const double *values, uint64_t n, uint64_t nnz, const int64_t *path_ptr,
+                                         const int64_t *path_nodes, uint64_t K, int32_t mode, void *out_tables,
+                                         int32_t device, g2n_wdist_info *info);
+
 /* ---- sequence distance (gfa2network/analysis.py:68-113 sequence_distance, `distance --seq`) -----
  * The fewest hops from any node whose sequence is seq_a to any node whose sequence is seq_b, over
  * the plain graph g2n_distances_from_path builds (of opts only directed, want_node_names, device,
