@@ -22,6 +22,9 @@
 //           zero queues v (one per node and level).  A queue that would overflow ends the launch
 //           after the level's expansion: seen / next are complete then, and the wide collect
 //           rebuilds the frontier from next.
+//   The two regimes' walks, queues and hand-over are the frontier_* templates below, which the
+//   weighted search (g2n_wdist.hip) runs with its own row bodies; the host's loop over them is
+//   run_frontier (g2n_queries.hip).
 // Accumulation, when v enters the frontier at level L with new bits B, for v's membership entries j:
 //   min   todo = B & ~done[j] (one load); if any, the bits the atomicOr on done[j] newly set store L
 //         into D[i][j] — each cell is written once, by one thread.
@@ -193,11 +196,16 @@ struct DistAcc {
   }
 };
 
-// wide: every node whose word in next is set joins level L's frontier (queue capacity n)
-__global__ void __launch_bounds__(256) k_dist_collect(unsigned long long* __restrict__ next, uint64_t n, uint32_t L,
-                                                      uint32_t* __restrict__ queue,
-                                                      unsigned long long* __restrict__ qmask, DistAcc acc,
-                                                      DistState* st) {
+// ---- the frontier skeleton: what the hop search and the weighted one (g2n_wdist.hip) share.  A
+// search supplies its row bodies as callables (inlined: a lambda of the kernel that calls); the walk
+// over the queue, the long-row hand-off, the LDS queues and the hand-over to the host live here.
+
+// wide: every node whose word in next is set joins level L's frontier (queue capacity n); the taker
+// of the word calls taken(v, bits, L)
+template <class Taken>
+__device__ __forceinline__ void frontier_collect(unsigned long long* __restrict__ next, uint64_t n, uint32_t L,
+                                                 uint32_t* __restrict__ queue, unsigned long long* __restrict__ qmask,
+                                                 DistState* st, Taken&& taken) {
   const uint64_t stride = (uint64_t)gridDim.x * 256;
   for (uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += stride) {
     if (!mask_ld(next + v)) continue;
@@ -211,30 +219,24 @@ __global__ void __launch_bounds__(256) k_dist_collect(unsigned long long* __rest
       st->level = L;
       st->last_level = L;
     }
-    acc.node((uint32_t)v, B, L);
+    taken((uint32_t)v, B, L);
   }
 }
 
-__device__ inline void dist_relax(unsigned long long* seen, unsigned long long* next, uint64_t v,
-                                  unsigned long long m) {
-  const unsigned long long nw = m & ~atomicOr(seen + v, m);
-  if (nw) atomicOr(next + v, nw);
-}
-
-template <class I>
-__global__ void __launch_bounds__(256) k_dist_expand(const I* __restrict__ indptr, const I* __restrict__ indices,
-                                                     uint64_t n, uint64_t nnz, unsigned long long* __restrict__ seen,
-                                                     unsigned long long* __restrict__ next,
-                                                     const uint32_t* __restrict__ queue,
-                                                     const unsigned long long* __restrict__ qmask,
-                                                     uint32_t* __restrict__ long_rows, uint64_t long_cap, DistState* st) {
+// wide: queue[0, count) by a thread per node — short_row(u, b, e, mask) for a row of at most
+// kStatsShortRow entries, a longer one goes to long_rows (its slot in the queue)
+template <class I, class Short>
+__device__ __forceinline__ void frontier_expand(const I* __restrict__ indptr, uint64_t n, uint64_t nnz,
+                                                const uint32_t* __restrict__ queue,
+                                                const unsigned long long* __restrict__ qmask,
+                                                uint32_t* __restrict__ long_rows, uint64_t long_cap, DistState* st,
+                                                Short&& short_row) {
   uint64_t count = st->count;
   if (count > n) count = n;
   const uint64_t stride = (uint64_t)gridDim.x * 256;
   for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < count; k += stride) {
     const uint64_t u = queue[k];
     if (u >= n) continue;
-    const unsigned long long m = qmask[k];
     uint64_t b, e;
     if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;
     if (e - b > kStatsShortRow) {
@@ -243,26 +245,18 @@ __global__ void __launch_bounds__(256) k_dist_expand(const I* __restrict__ indpt
       else st->bad = 1u;
       continue;
     }
-    for (uint64_t j = b; j < e; j++) {
-      const uint64_t c = (uint64_t)indices[j];
-      if (c >= n) {
-        st->bad = 1u;
-        continue;
-      }
-      dist_relax(seen, next, c, m);
-    }
+    short_row(u, b, e, qmask[k]);
   }
 }
 
-template <class I>
-__global__ void __launch_bounds__(256) k_dist_expand_long(const I* __restrict__ indptr, const I* __restrict__ indices,
-                                                          uint64_t n, uint64_t nnz,
-                                                          unsigned long long* __restrict__ seen,
-                                                          unsigned long long* __restrict__ next,
-                                                          const uint32_t* __restrict__ queue,
-                                                          const unsigned long long* __restrict__ qmask,
-                                                          const uint32_t* __restrict__ long_rows, uint64_t long_cap,
-                                                          DistState* st) {
+// wide: long_rows by a block per row — long_row(u, b, e, mask), the whole block together (everything
+// up to the row is the block's: no thread leaves alone, a row body may use __syncthreads())
+template <class I, class Long>
+__device__ __forceinline__ void frontier_expand_long(const I* __restrict__ indptr, uint64_t n, uint64_t nnz,
+                                                     const uint32_t* __restrict__ queue,
+                                                     const unsigned long long* __restrict__ qmask,
+                                                     const uint32_t* __restrict__ long_rows, uint64_t long_cap,
+                                                     DistState* st, Long&& long_row) {
   uint64_t n_long = st->n_long, count = st->count;
   if (n_long > long_cap) n_long = long_cap;
   if (count > n) count = n;
@@ -271,39 +265,32 @@ __global__ void __launch_bounds__(256) k_dist_expand_long(const I* __restrict__ 
     if (k >= count) continue;
     const uint64_t u = queue[k];
     if (u >= n) continue;
-    const unsigned long long m = qmask[k];
     uint64_t b, e;
     if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;
-    for (uint64_t j = b + threadIdx.x; j < e; j += 256) {
-      const uint64_t c = (uint64_t)indices[j];
-      if (c >= n) {
-        st->bad = 1u;
-        continue;
-      }
-      dist_relax(seen, next, c, m);
-    }
+    long_row(u, b, e, qmask[k]);
   }
 }
 
-// narrow: one workgroup, from the collected frontier in queue / qmask (st->count <= kDistNarrowCap
-// nodes of level st->level) until the frontier empties (count = 0), a queue would overflow (pending
-// = 1: next holds level `level`, uncollected) or `budget` levels have run (the frontier is written
-// back to queue / qmask).
-template <class I>
-__global__ void __launch_bounds__(kDistNarrowTPB) k_dist_narrow(const I* __restrict__ indptr,
-                                                                const I* __restrict__ indices, uint64_t n, uint64_t nnz,
-                                                                unsigned long long* __restrict__ seen,
-                                                                unsigned long long* __restrict__ next,
-                                                                uint32_t* __restrict__ queue,
-                                                                unsigned long long* __restrict__ qmask, DistAcc acc,
-                                                                DistState* st, uint32_t budget) {
+// narrow: one workgroup of kDistNarrowTPB threads, from the collected frontier in queue / qmask
+// (st->count <= kDistNarrowCap nodes of level st->level) until the frontier empties (count = 0), a
+// queue would overflow (pending = 1: next holds level `level`'s discoveries, uncollected) or `budget`
+// levels have run (the frontier is written back to queue / qmask).
+//   short_row(u, b, e, mask, push) by one thread, long_row(u, b, e, mask, push) by the block (the same
+//   arguments in every thread).  push(c, bits) sets bits in next[c]; the thread that found the word
+//   zero queues c for the next level (one per node and level).
+//   taken(v, bits, L): v's word was taken — it is in level L's frontier with those bits.
+template <class I, class Short, class Long, class Taken>
+__device__ __forceinline__ void frontier_narrow(const I* __restrict__ indptr, uint64_t n, uint64_t nnz,
+                                                unsigned long long* __restrict__ next, uint32_t* __restrict__ queue,
+                                                unsigned long long* __restrict__ qmask, DistState* st, uint32_t budget,
+                                                Short&& short_row, Long&& long_row, Taken&& taken) {
   __shared__ unsigned long long qm[2][kDistNarrowCap];
   __shared__ uint32_t qv[2][kDistNarrowCap];
   __shared__ uint32_t s_long[kDistNarrowCap];  // frontier slots whose row the whole block walks
   __shared__ uint32_t s_cnt[2], s_nlong, s_over;
   const uint32_t tid = threadIdx.x;
   uint32_t cnt = st->count, L = st->level, cur = 0;
-  if (cnt > kDistNarrowCap) return;  // (the host launches it only below the cap)
+  if (cnt > kDistNarrowCap || budget == 0) return;  // (the host launches it only below the cap)
   for (uint32_t k = tid; k < cnt; k += kDistNarrowTPB) {
     qv[0][k] = queue[k];
     qm[0][k] = qmask[k];
@@ -314,20 +301,14 @@ __global__ void __launch_bounds__(kDistNarrowTPB) k_dist_narrow(const I* __restr
     s_over = 0;
   }
   __syncthreads();
-  auto relax = [&](uint64_t c, unsigned long long m, uint32_t nx) {
-    if (c >= n) {
-      st->bad = 1u;
-      return;
-    }
-    const unsigned long long nw = m & ~atomicOr(seen + c, m);
-    if (!nw) return;
-    if (atomicOr(next + c, nw)) return;  // queued by the thread that found the word zero
-    const uint32_t p = atomicAdd(&s_cnt[nx], 1u);
-    if (p < kDistNarrowCap) qv[nx][p] = (uint32_t)c;
-    else s_over = 1u;
-  };
   for (uint32_t it = 0;; it++) {
     const uint32_t nx = cur ^ 1u;
+    auto push = [&](uint64_t c, unsigned long long bits) {
+      if (atomicOr(next + c, bits)) return;  // queued by the thread that found the word zero
+      const uint32_t p = atomicAdd(&s_cnt[nx], 1u);
+      if (p < kDistNarrowCap) qv[nx][p] = (uint32_t)c;
+      else s_over = 1u;
+    };
     // ---- expand level L: short rows by a thread each, longer ones by the block
     for (uint32_t k = tid; k < cnt; k += kDistNarrowTPB) {
       const uint64_t u = qv[cur][k];
@@ -337,21 +318,19 @@ __global__ void __launch_bounds__(kDistNarrowTPB) k_dist_narrow(const I* __restr
         s_long[atomicAdd(&s_nlong, 1u)] = k;  // (at most cnt <= kDistNarrowCap of them)
         continue;
       }
-      const unsigned long long m = qm[cur][k];
-      for (uint64_t j = b; j < e; j++) relax((uint64_t)indices[j], m, nx);
+      short_row(u, b, e, qm[cur][k], push);
     }
     __syncthreads();
     const uint32_t nl = s_nlong;
     for (uint32_t w = 0; w < nl; w++) {
       const uint32_t k = s_long[w];
       const uint64_t u = qv[cur][k];
-      const unsigned long long m = qm[cur][k];
       uint64_t b, e;
-      if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;
-      for (uint64_t j = b + tid; j < e; j += kDistNarrowTPB) relax((uint64_t)indices[j], m, nx);
+      if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;  // (the same answer in every thread)
+      long_row(u, b, e, qm[cur][k], push);
     }
     __syncthreads();
-    // every atomic of the level has returned: seen / next are complete for level L + 1
+    // every atomic of the level has returned: the search's state and next are complete for level L + 1
     const uint32_t ncnt = s_cnt[nx], over = s_over;
     L++;
     if (over) {
@@ -371,12 +350,12 @@ __global__ void __launch_bounds__(kDistNarrowTPB) k_dist_narrow(const I* __restr
       }
       return;
     }
-    // ---- collect level L + 1: take each queued node's word and accumulate
+    // ---- collect level L + 1: take each queued node's word
     for (uint32_t k = tid; k < ncnt; k += kDistNarrowTPB) {
       const uint32_t v = qv[nx][k];
       const unsigned long long B = atomicExch(next + v, 0ull);
       qm[nx][k] = B;
-      acc.node(v, B, L);
+      taken(v, B, L);
     }
     if (tid == 0) {
       s_cnt[cur] = 0;
@@ -399,6 +378,82 @@ __global__ void __launch_bounds__(kDistNarrowTPB) k_dist_narrow(const I* __restr
       return;
     }
   }
+}
+
+// ---- the hop search's kernels over the skeleton
+
+__global__ void __launch_bounds__(256) k_dist_collect(unsigned long long* __restrict__ next, uint64_t n, uint32_t L,
+                                                      uint32_t* __restrict__ queue,
+                                                      unsigned long long* __restrict__ qmask, DistAcc acc,
+                                                      DistState* st) {
+  frontier_collect(next, n, L, queue, qmask, st,
+                   [&](uint32_t v, unsigned long long B, uint32_t lv) { acc.node(v, B, lv); });
+}
+
+// entries [b, e) from b + first by step: the paths of m not yet seen at an entry's column are its
+// discoveries — found(c, those bits)
+template <class I, class F>
+__device__ __forceinline__ void dist_relax_row(const I* __restrict__ indices, uint64_t n, uint64_t b, uint64_t e,
+                                               uint32_t first, uint32_t step, unsigned long long m,
+                                               unsigned long long* seen, DistState* st, F&& found) {
+  for (uint64_t j = b + first; j < e; j += step) {
+    const uint64_t c = (uint64_t)indices[j];
+    if (c >= n) {
+      st->bad = 1u;
+      continue;
+    }
+    const unsigned long long nw = m & ~atomicOr(seen + c, m);
+    if (nw) found(c, nw);
+  }
+}
+
+template <class I>
+__global__ void __launch_bounds__(256) k_dist_expand(const I* __restrict__ indptr, const I* __restrict__ indices,
+                                                     uint64_t n, uint64_t nnz, unsigned long long* __restrict__ seen,
+                                                     unsigned long long* __restrict__ next,
+                                                     const uint32_t* __restrict__ queue,
+                                                     const unsigned long long* __restrict__ qmask,
+                                                     uint32_t* __restrict__ long_rows, uint64_t long_cap, DistState* st) {
+  const auto found = [&](uint64_t c, unsigned long long nw) { atomicOr(next + c, nw); };
+  frontier_expand(indptr, n, nnz, queue, qmask, long_rows, long_cap, st,
+                  [&](uint64_t, uint64_t b, uint64_t e, unsigned long long m) {
+                    dist_relax_row(indices, n, b, e, 0u, 1u, m, seen, st, found);
+                  });
+}
+
+template <class I>
+__global__ void __launch_bounds__(256) k_dist_expand_long(const I* __restrict__ indptr, const I* __restrict__ indices,
+                                                          uint64_t n, uint64_t nnz,
+                                                          unsigned long long* __restrict__ seen,
+                                                          unsigned long long* __restrict__ next,
+                                                          const uint32_t* __restrict__ queue,
+                                                          const unsigned long long* __restrict__ qmask,
+                                                          const uint32_t* __restrict__ long_rows, uint64_t long_cap,
+                                                          DistState* st) {
+  const auto found = [&](uint64_t c, unsigned long long nw) { atomicOr(next + c, nw); };
+  frontier_expand_long(indptr, n, nnz, queue, qmask, long_rows, long_cap, st,
+                       [&](uint64_t, uint64_t b, uint64_t e, unsigned long long m) {
+                         dist_relax_row(indices, n, b, e, threadIdx.x, 256u, m, seen, st, found);
+                       });
+}
+
+template <class I>
+__global__ void __launch_bounds__(kDistNarrowTPB) k_dist_narrow(const I* __restrict__ indptr,
+                                                                const I* __restrict__ indices, uint64_t n, uint64_t nnz,
+                                                                unsigned long long* __restrict__ seen,
+                                                                unsigned long long* __restrict__ next,
+                                                                uint32_t* __restrict__ queue,
+                                                                unsigned long long* __restrict__ qmask, DistAcc acc,
+                                                                DistState* st, uint32_t budget) {
+  frontier_narrow(
+      indptr, n, nnz, next, queue, qmask, st, budget,
+      [&](uint64_t, uint64_t b, uint64_t e, unsigned long long m, auto& push) {
+        dist_relax_row(indices, n, b, e, 0u, 1u, m, seen, st, push);
+      },
+      [&](uint64_t, uint64_t b, uint64_t e, unsigned long long m, auto& push) {
+        dist_relax_row(indices, n, b, e, threadIdx.x, kDistNarrowTPB, m, seen, st, push);
+      },
+      [&](uint32_t v, unsigned long long B, uint32_t L) { acc.node(v, B, L); });
 }
 
 // keys [offs[i], offs[i + 1]) of blob: *flag = 1 when one ends in ":+" or ":-" (the reference's

@@ -2278,877 +2278,12 @@ static void download_result(g2n_context* c, const g2n_result& D, HostResult* H) 
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
-// --------------------------------------------------------- graph statistics ------
-// g2n_csr_stats on c's stream (the caller holds c's lock and opened the call).
-template <class I>
-static void csr_stats_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz, bool directed,
-                        StatsOut* so, hipEvent_t* ev) {
-  auto* parent = dget<uint32_t>(c, S_STPARENT, n);
-  auto* diag = dget<uint8_t>(c, S_STDIAG, n);
-  uint32_t* colcnt = directed ? dget<uint32_t>(c, S_STCOL, n) : nullptr;
-  const uint64_t long_cap = nnz / kStatsShortRow + 1;
-  auto* long_rows = dget<uint32_t>(c, S_STLONG, long_cap);
-  const unsigned g = grid_for(n);
-  const unsigned gr = (unsigned)std::min<uint64_t>(g, (uint64_t)c->n_cu * 8);
-  // ---- degrees (this walk also queues the long rows for both walks)
-  G2N_HIP(hipEventRecord(ev[0], c->stream));
-  G2N_HIP(hipMemsetAsync(diag, 0, n, c->stream));
-  if (colcnt) G2N_HIP(hipMemsetAsync(colcnt, 0, n * sizeof(uint32_t), c->stream));
-  const DegOp dop{diag, colcnt};
-  hipLaunchKernelGGL((k_rows_short<I, DegOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, dop, 1,
-                     long_rows, long_cap, so);
-  hipLaunchKernelGGL((k_rows_long<I, DegOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, dop,
-                     (const uint32_t*)long_rows, long_cap, so);
-  hipLaunchKernelGGL(k_deg_max<I>, dim3(gr), dim3(256), 0, c->stream, indptr, n, nnz, (const uint8_t*)diag,
-                     (const uint32_t*)colcnt, so);
-  G2N_HIP(hipEventRecord(ev[1], c->stream));
-  // ---- components
-  const HookOp hop{parent};
-  hipLaunchKernelGGL(k_cc_init<I>, dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, parent, so);
-  hipLaunchKernelGGL((k_rows_short<I, HookOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop, 0,
-                     long_rows, long_cap, so);
-  hipLaunchKernelGGL((k_rows_long<I, HookOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop,
-                     (const uint32_t*)long_rows, long_cap, so);
-  hipLaunchKernelGGL(k_cc_flatten, dim3(gr), dim3(256), 0, c->stream, parent, n, so);
-  G2N_HIP(hipEventRecord(ev[2], c->stream));
-}
+}  // namespace g2n
 
-static StatsOut* stats_out_reset(g2n_context* c) {
-  auto* so = dget<StatsOut>(c, S_STOUT, 1);
-  G2N_HIP(hipMemsetAsync(so, 0, sizeof(StatsOut), c->stream));
-  G2N_HIP(hipMemsetAsync(&so->high_off, 0xFF, sizeof(so->high_off), c->stream));
-  return so;
-}
+// the queries over a finished CSR (stats, path distances) and the results of the host builds that ask for one
+#include "g2n_queries.hip"
 
-static void csr_stats(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
-                      uint64_t nnz, int32_t directed, g2n_graph_stats* out) {
-  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, "g2n_csr_stats: index_width must be 4 or 8");
-  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats: 2^31-1 or more nodes");
-  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats: 2^32-1 or more entries");
-  std::memset(out, 0, sizeof(*out));
-  out->n_nodes = (int64_t)n;
-  out->n_entries = (int64_t)nnz;
-  if (n == 0) {
-    if (nnz) throw Failure(G2N_E_ARG, "g2n_csr_stats: entries without rows");
-    return;
-  }
-  if (!indptr || (nnz && !indices)) throw Failure(G2N_E_ARG, "g2n_csr_stats: null array");
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
-  StatsOut* so = stats_out_reset(c);
-  if (index_width == 4)
-    csr_stats_t<int32_t>(c, (const int32_t*)indptr, (const int32_t*)indices, n, nnz, directed != 0, so, ev.e);
-  else
-    csr_stats_t<int64_t>(c, (const int64_t*)indptr, (const int64_t*)indices, n, nnz, directed != 0, so, ev.e);
-  const StatsOut h = read_dev(c, so);
-  if (h.bad) throw Failure(G2N_E_ARG, "g2n_csr_stats: indptr / indices out of range");
-  float ms = 0.f;
-  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  out->ms_degree = ms;
-  G2N_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
-  out->ms_components = ms;
-  out->n_diag = (int64_t)h.n_diag;
-  out->n_components = (int64_t)h.n_roots;
-  out->max_degree = (int64_t)h.max_degree;
-}
-
-int csr_stats_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
-                   int32_t directed, int32_t device, g2n_graph_stats* out) {
-  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, "g2n_csr_stats_host: index_width must be 4 or 8");
-  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats_host: 2^31-1 or more nodes");
-  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_stats_host: 2^32-1 or more entries");
-  if (!indptr || (nnz && !indices)) throw Failure(G2N_E_ARG, "g2n_csr_stats_host: null array");
-  g2n_context* c = shared_context(device);
-  std::lock_guard<std::mutex> lk(c->mu);
-  enter_call(c);
-  G2N_HIP(hipSetDevice(c->device));
-  clear_call_state(c);
-  const size_t w = (size_t)index_width;
-  void* dip = dbuf(c, S_STIP, (size_t)(n + 1) * w);
-  void* dix = dbuf(c, S_STIX, (size_t)nnz * w);
-  G2N_HIP(hipMemcpyAsync(dip, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
-  if (nnz) G2N_HIP(hipMemcpyAsync(dix, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
-  csr_stats(c, dip, dix, index_width, n, nnz, directed, out);
-  shrink_shared(c);
-  return G2N_OK;
-}
-
-// --------------------------------------------------------- path distances ------
-// g2n_csr_path_distances on c's stream (the caller holds c's lock and opened the call); tables: device.
-template <class I>
-static void path_distances_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz,
-                             const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, uint64_t steps, bool mean,
-                             void* tables, g2n_dist_info* info) {
-  auto* st = dget<DistState>(c, S_DSTATE, 1);
-  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  // ---- the caller's arrays, checked whole; the steps' paths and the nodes' step counts
-  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
-  auto* mem_ptr = dget<uint32_t>(c, S_DMPTR, n + 1);
-  auto* cursor = dget<uint32_t>(c, S_DCUR, n + 1);
-  auto* mem_path = dget<uint32_t>(c, S_DMPATH, steps);
-  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
-  G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
-                     indices, n, nnz, st);
-  hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
-  if (steps)
-    hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
-                       step_path, cnt, st);
-  if (read_dev(c, st).bad)
-    throw Failure(G2N_E_ARG, "g2n_csr_path_distances: indptr / indices / path_ptr / path_nodes out of range");
-  // ---- membership: the steps sorted by node
-  scan_excl<uint32_t, uint32_t>(c, cnt, mem_ptr, n + 1);
-  G2N_HIP(hipMemcpyAsync(cursor, mem_ptr, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-  if (steps)
-    hipLaunchKernelGGL(k_dist_fill, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
-                       (const uint32_t*)step_path, cursor, mem_path);
-  // ---- tables
-  DistAcc acc{mem_ptr, mem_path, nullptr, nullptr, nullptr, nullptr, K, 0};
-  if (mean) {
-    acc.S = (unsigned long long*)tables;
-    acc.C = acc.S + K * K;
-    G2N_HIP(hipMemsetAsync(tables, 0, K * K * 16, c->stream));
-  } else {
-    acc.D = (uint32_t*)tables;
-    acc.done = dget<unsigned long long>(c, S_DDONE, K);
-    G2N_HIP(hipMemsetAsync(tables, 0xFF, K * K * 4, c->stream));
-  }
-  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
-  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
-  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
-  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
-  const uint64_t long_cap = nnz / kStatsShortRow + 1;
-  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
-  std::vector<int64_t> h_ptr(K + 1);
-  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  const unsigned gn = std::min(grid_for(n), gcap);
-  int64_t launches = 0, levels = 0, batches = 0;
-  for (uint64_t base = 0; base < K; base += 64, batches++) {
-    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[std::min<uint64_t>(base + 64, K)];
-    acc.base = (uint32_t)base;
-    G2N_HIP(hipMemsetAsync(seen, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
-    if (acc.done) G2N_HIP(hipMemsetAsync(acc.done, 0, K * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-    if (s1 > s0) {
-      hipLaunchKernelGGL(k_dist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
-                         (const uint32_t*)step_path, (uint32_t)base, seen, next);
-      launches++;
-    }
-    uint32_t L = 0;
-    for (bool more = s1 > s0; more;) {
-      // wide: level L's frontier from next (count, n_long, pending cleared first)
-      G2N_HIP(hipMemsetAsync(st, 0, 3 * sizeof(uint32_t), c->stream));
-      hipLaunchKernelGGL(k_dist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc, st);
-      launches++;
-      DistState h = read_dev(c, st);
-      if (h.count == 0) break;
-      if (h.count > kDistNarrowCap) {
-        hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(h.count), gcap)), dim3(256), 0, c->stream, indptr,
-                           indices, n, nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
-                           long_rows, long_cap, st);
-        hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
-                           nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
-                           (const uint32_t*)long_rows, long_cap, st);
-        launches += 2;
-        L++;
-        continue;
-      }
-      // narrow: one workgroup carries it until it empties, overflows or has run its budget
-      for (;;) {
-        hipLaunchKernelGGL(k_dist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n, nnz, seen,
-                           next, queue, qmask, acc, st, kDistLevelBudget);
-        launches++;
-        h = read_dev(c, st);
-        if (h.pending) {
-          L = h.level;
-          break;
-        }
-        if (h.count == 0) {
-          more = false;
-          break;
-        }
-        if (h.count > kDistNarrowCap) throw Failure(G2N_E_DEVICE, "g2n_csr_path_distances: frontier state");
-      }
-    }
-    const DistState h = read_dev(c, st);
-    if (h.bad) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: indptr / indices out of range");
-    levels = std::max<int64_t>(levels, h.last_level);
-  }
-  info->levels = levels;
-  info->launches = launches;
-  info->batches = batches;
-}
-
-static void path_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
-                           uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
-                           void* tables, g2n_dist_info* info) {
-  if (index_width != 4 && index_width != 8)
-    throw Failure(G2N_E_ARG, "g2n_csr_path_distances: index_width must be 4 or 8");
-  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: unknown mode");
-  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: 2^31-1 or more nodes");
-  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: 2^32-1 or more entries");
-  std::memset(info, 0, sizeof(*info));
-  if (K == 0) return;
-  if (!path_ptr || !tables) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: null array");
-  if ((n && !indptr) || (nnz && !indices)) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: null array");
-  if (n == 0 && nnz) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: entries without rows");
-  int64_t ends[2];
-  G2N_HIP(hipMemcpyAsync(&ends[0], path_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipMemcpyAsync(&ends[1], path_ptr + K, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  if (ends[0] != 0 || ends[1] < 0) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: path_ptr out of range");
-  const uint64_t steps = (uint64_t)ends[1];
-  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: 2^32-1 or more steps");
-  if (steps && !path_nodes) throw Failure(G2N_E_ARG, "g2n_csr_path_distances: null array");
-  struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
-  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
-  if (index_width == 4)
-    path_distances_t<int32_t>(c, (const int32_t*)indptr, (const int32_t*)indices, n, nnz, path_ptr, path_nodes, K, steps,
-                              mode == G2N_DIST_MEAN, tables, info);
-  else
-    path_distances_t<int64_t>(c, (const int64_t*)indptr, (const int64_t*)indices, n, nnz, path_ptr, path_nodes, K, steps,
-                              mode == G2N_DIST_MEAN, tables, info);
-  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  info->ms_bfs = ms;
-}
-
-// bytes of the tables of K paths (mean: S then C, uint64 each; min: D, uint32); 0 = past 2^63
-static uint64_t dist_table_bytes(uint64_t K, int32_t mode) {
-  if (K >= (1ull << 29)) return 0;
-  return K * K * (mode == G2N_DIST_MEAN ? 16 : 4);
-}
-
-// the three K x K tables of one call must fit the device's free memory
-static void dist_check_k(uint64_t K, int32_t mode) {
-  size_t f = 0, t = 0;
-  G2N_HIP(hipMemGetInfo(&f, &t));
-  const uint64_t want = dist_table_bytes(K, mode);
-  if ((K && !want) || want + K * 8 > f)
-    throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances: the K x K tables of " + std::to_string(K) +
-                                         " paths exceed the device's free memory");
-}
-
-int csr_path_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
-                            const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
-                            void* out_tables, int32_t device, g2n_dist_info* info) {
-  if (index_width != 4 && index_width != 8)
-    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: index_width must be 4 or 8");
-  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN)
-    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: unknown mode");
-  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_host: 2^31-1 or more nodes");
-  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_host: 2^32-1 or more entries");
-  if (!indptr || (nnz && !indices) || !path_ptr || (K && !out_tables))
-    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: null array");
-  if (path_ptr[0] != 0 || path_ptr[K] < 0 || (path_ptr[K] && !path_nodes))
-    throw Failure(G2N_E_ARG, "g2n_csr_path_distances_host: path_ptr out of range");
-  const uint64_t steps = (uint64_t)path_ptr[K];
-  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_host: 2^32-1 or more steps");
-  g2n_context* c = shared_context(device);
-  std::lock_guard<std::mutex> lk(c->mu);
-  enter_call(c);
-  G2N_HIP(hipSetDevice(c->device));
-  clear_call_state(c);
-  dist_check_k(K, mode);
-  const size_t w = (size_t)index_width;
-  void* dip = dbuf(c, S_STIP, (size_t)(n + 1) * w);
-  void* dix = dbuf(c, S_STIX, (size_t)nnz * w);
-  auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
-  auto* dpn = dget<int64_t>(c, S_DPN, steps);
-  const uint64_t tbytes = dist_table_bytes(K, mode);
-  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
-  G2N_HIP(hipMemcpyAsync(dip, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
-  if (nnz) G2N_HIP(hipMemcpyAsync(dix, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
-  G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
-  path_distances(c, dip, dix, index_width, n, nnz, dpp, dpn, K, mode, dtab, info);
-  if (tbytes) G2N_HIP(hipMemcpyAsync(out_tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  shrink_shared(c);
-  return G2N_OK;
-}
-
-// ------------------------------------------------ weighted path distances ------
-// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
-// tables: device.  Nothing is written to the tables before every array has passed its check.
-template <class I>
-static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
-                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
-                              uint64_t steps, bool mean, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
-  const char* who = "g2n_csr_path_distances_weighted";
-  auto* st = dget<DistState>(c, S_DSTATE, 1);
-  G2N_HIP(hipEventRecord(ev[0], c->stream));
-  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  // ---- the caller's arrays, checked whole; the steps' paths
-  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
-  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
-  G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
-                     indices, n, nnz, st);
-  if (nnz)
-    hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for(nnz), gcap)), dim3(256), 0, c->stream, values, nnz, st);
-  hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
-  if (steps)
-    hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
-                       step_path, cnt, st);
-  if (read_dev(c, st).bad)
-    throw Failure(G2N_E_ARG, std::string(who) + ": indptr / indices / path_ptr / path_nodes out of range, or a value "
-                                                "that is negative or not finite");
-  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
-  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
-  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
-  const uint64_t long_cap = nnz / kStatsShortRow + 1;
-  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
-  // ---- B paths a batch: B * n distances must fit what is free (and what the slot already holds)
-  uint64_t B = std::min<uint64_t>(64, K);
-  if (n) {
-    size_t f = 0, t = 0;
-    G2N_HIP(hipMemGetInfo(&f, &t));
-    const uint64_t avail = (uint64_t)f + c->bufs[S_WDIST].cap;
-    B = std::min<uint64_t>(B, avail / 10 * 8 / (n * 8));  // (the arena adds an eighth to what it is asked for)
-    if (B == 0)
-      throw Failure(G2N_E_UNSUPPORTED, std::string(who) + ": the distances of one path over " + std::to_string(n) +
-                                           " nodes exceed the device's free memory");
-  }
-  auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
-  info->batch_paths = (int64_t)B;
-  // ---- tables
-  auto* D = (unsigned long long*)tables;
-  if (!mean)
-    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(K * K), gcap)), dim3(256), 0, c->stream, D, K * K,
-                       kWDistInf);
-  std::vector<int64_t> h_ptr(K + 1);
-  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  const unsigned gn = std::min(grid_for(n), gcap);
-  int64_t launches = 0, rounds = 0, batches = 0;
-  double ms_search = 0.0, ms_tables = 0.0;
-  for (uint64_t base = 0; base < K; base += B, batches++) {
-    const uint64_t nb = std::min<uint64_t>(B, K - base);
-    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[base + nb];
-    if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
-    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(n * B), gcap)), dim3(256), 0, c->stream, dist, n * B,
-                       kWDistInf);
-    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-    launches++;
-    if (s1 > s0) {
-      hipLaunchKernelGGL(k_wdist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
-                         (const uint32_t*)step_path, (uint32_t)base, (uint32_t)B, dist, next);
-      launches++;
-    }
-    // round R expands the nodes that round R - 1 improved; the last one that improves anything is
-    // at most n - 1 (g2n_wdist.hip), so a frontier of a round past n is a failure, not a reason to go on
-    uint64_t R = 0;
-    for (bool more = s1 > s0; more;) {
-      if (R > n) throw Failure(G2N_E_DEVICE, std::string(who) + ": did not converge in n rounds");
-      // wide: round R's frontier from next (count, n_long, pending cleared first)
-      G2N_HIP(hipMemsetAsync(st, 0, 3 * sizeof(uint32_t), c->stream));
-      hipLaunchKernelGGL(k_wdist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, (uint32_t)R, queue, qmask, st);
-      launches++;
-      DistState h = read_dev(c, st);
-      if (h.count == 0) break;
-      if (h.count > kDistNarrowCap) {
-        hipLaunchKernelGGL(k_wdist_expand<I>, dim3(std::min(grid_for(h.count), gcap)), dim3(256), 0, c->stream, indptr,
-                           indices, values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
-                           (const unsigned long long*)qmask, long_rows, long_cap, st);
-        hipLaunchKernelGGL(k_wdist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices,
-                           values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
-                           (const unsigned long long*)qmask, (const uint32_t*)long_rows, long_cap, st);
-        launches += 2;
-        R++;
-        continue;
-      }
-      // narrow: one workgroup carries it until it empties, overflows or has run its budget
-      for (;;) {
-        const uint32_t budget = (uint32_t)std::min<uint64_t>(kWDistRoundBudget, n + 1 - R);  // (R <= n: >= 1)
-        hipLaunchKernelGGL(k_wdist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, values, n,
-                           nnz, (uint32_t)B, dist, next, queue, qmask, st, budget);
-        launches++;
-        h = read_dev(c, st);
-        if (h.level <= R || h.level > R + budget) throw Failure(G2N_E_DEVICE, std::string(who) + ": frontier state");
-        R = h.level;
-        if (h.pending) break;
-        if (h.count == 0) {
-          more = false;
-          break;
-        }
-        if (h.count > kDistNarrowCap) throw Failure(G2N_E_DEVICE, std::string(who) + ": frontier state");
-        if (R > n) throw Failure(G2N_E_DEVICE, std::string(who) + ": did not converge in n rounds");
-      }
-    }
-    const DistState h = read_dev(c, st);
-    if (h.bad) throw Failure(G2N_E_ARG, std::string(who) + ": indptr / indices out of range");
-    rounds = std::max<int64_t>(rounds, h.last_level);
-    // ---- the batch's rows of the tables
-    G2N_HIP(hipEventRecord(ev[1], c->stream));
-    if (mean)
-      hipLaunchKernelGGL(k_wdist_mean, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes, steps, n,
-                         K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base, (double*)tables,
-                         D + K * K);
-    else if (steps)
-      hipLaunchKernelGGL(k_wdist_min, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
-                         (const uint32_t*)step_path, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb,
-                         (uint32_t)base, D);
-    launches++;
-    G2N_HIP(hipEventRecord(ev[2], c->stream));
-    G2N_HIP(hipEventSynchronize(ev[2]));
-    float ms = 0.f;
-    G2N_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ms_search += ms;
-    G2N_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    ms_tables += ms;
-  }
-  info->rounds = rounds;
-  info->launches = launches;
-  info->batches = batches;
-  info->ms_search = ms_search;
-  info->ms_tables = ms_tables;
-}
-
-static void wpath_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width,
-                            const double* values, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
-                            const int64_t* path_nodes, uint64_t K, int32_t mode, void* tables, g2n_wdist_info* info) {
-  const std::string who = "g2n_csr_path_distances_weighted";
-  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, who + ": index_width must be 4 or 8");
-  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, who + ": unknown mode");
-  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^31-1 or more nodes");
-  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more entries");
-  std::memset(info, 0, sizeof(*info));
-  info->batch_paths = (int64_t)std::max<uint64_t>(1, std::min<uint64_t>(64, K));
-  if (K == 0) return;
-  if (!path_ptr || !tables) throw Failure(G2N_E_ARG, who + ": null array");
-  if ((n && !indptr) || (nnz && (!indices || !values))) throw Failure(G2N_E_ARG, who + ": null array");
-  if (n == 0 && nnz) throw Failure(G2N_E_ARG, who + ": entries without rows");
-  int64_t ends[2];
-  G2N_HIP(hipMemcpyAsync(&ends[0], path_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipMemcpyAsync(&ends[1], path_ptr + K, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  if (ends[0] != 0 || ends[1] < 0) throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
-  const uint64_t steps = (uint64_t)ends[1];
-  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
-  if (steps && !path_nodes) throw Failure(G2N_E_ARG, who + ": null array");
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
-  if (index_width == 4)
-    wpath_distances_t<int32_t>(c, (const int32_t*)indptr, (const int32_t*)indices, values, n, nnz, path_ptr, path_nodes,
-                               K, steps, mode == G2N_DIST_MEAN, tables, info, ev.e);
-  else
-    wpath_distances_t<int64_t>(c, (const int64_t*)indptr, (const int64_t*)indices, values, n, nnz, path_ptr, path_nodes,
-                               K, steps, mode == G2N_DIST_MEAN, tables, info, ev.e);
-  G2N_HIP(hipStreamSynchronize(c->stream));
-}
-
-// bytes of the weighted tables of K paths (mean: S float64 then C uint64; min: D float64); 0 = past 2^63
-static uint64_t wdist_table_bytes(uint64_t K, int32_t mode) {
-  if (K >= (1ull << 29)) return 0;
-  return K * K * (mode == G2N_DIST_MEAN ? 16 : 8);
-}
-
-static void wdist_check_k(uint64_t K, int32_t mode) {
-  size_t f = 0, t = 0;
-  G2N_HIP(hipMemGetInfo(&f, &t));
-  const uint64_t want = wdist_table_bytes(K, mode);
-  if ((K && !want) || want + K * 8 > f)
-    throw Failure(G2N_E_UNSUPPORTED, "g2n_csr_path_distances_weighted: the K x K tables of " + std::to_string(K) +
-                                         " paths exceed the device's free memory");
-}
-
-int csr_path_distances_weighted_host(const void* indptr, const void* indices, int32_t index_width, const double* values,
-                                     uint64_t n, uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes,
-                                     uint64_t K, int32_t mode, void* out_tables, int32_t device, g2n_wdist_info* info) {
-  const std::string who = "g2n_csr_path_distances_weighted_host";
-  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, who + ": index_width must be 4 or 8");
-  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, who + ": unknown mode");
-  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^31-1 or more nodes");
-  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more entries");
-  if (!indptr || (nnz && (!indices || !values)) || !path_ptr || (K && !out_tables))
-    throw Failure(G2N_E_ARG, who + ": null array");
-  if (path_ptr[0] != 0 || path_ptr[K] < 0 || (path_ptr[K] && !path_nodes))
-    throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
-  const uint64_t steps = (uint64_t)path_ptr[K];
-  if (steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
-  g2n_context* c = shared_context(device);
-  std::lock_guard<std::mutex> lk(c->mu);
-  enter_call(c);
-  G2N_HIP(hipSetDevice(c->device));
-  clear_call_state(c);
-  wdist_check_k(K, mode);
-  const size_t w = (size_t)index_width;
-  void* dip = dbuf(c, S_STIP, (size_t)(n + 1) * w);
-  void* dix = dbuf(c, S_STIX, (size_t)nnz * w);
-  auto* dval = dget<double>(c, S_WVAL, nnz);
-  auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
-  auto* dpn = dget<int64_t>(c, S_DPN, steps);
-  const uint64_t tbytes = wdist_table_bytes(K, mode);
-  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
-  G2N_HIP(hipMemcpyAsync(dip, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
-  if (nnz) G2N_HIP(hipMemcpyAsync(dix, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
-  if (nnz) G2N_HIP(hipMemcpyAsync(dval, values, (size_t)nnz * 8, hipMemcpyHostToDevice, c->stream));
-  G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
-  wpath_distances(c, dip, dix, index_width, dval, n, nnz, dpp, dpn, K, mode, dtab, info);
-  if (tbytes) G2N_HIP(hipMemcpyAsync(out_tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  shrink_shared(c);
-  return G2N_OK;
-}
-
-static thread_local const StatsRequest* t_stats_request = nullptr;
-void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
-static thread_local const DistRequest* t_dist_request = nullptr;
-void set_dist_request(const DistRequest* req) { t_dist_request = req; }
-static thread_local const SeqRequest* t_seq_request = nullptr;
-void set_seq_request(const SeqRequest* req) { t_seq_request = req; }
-
-// H's result as D's scalars, no matrix and no names (a stats or distance request's build)
-static void scalars_result(g2n_context* c, const g2n_result& D, HostResult* H) {
-  g2n_result& R = H->r;
-  std::memcpy(&R, &D, sizeof(g2n_result));
-  R.priv_ = H;
-  R.err_detail = nullptr;
-  R.names_blob = nullptr;
-  R.names_offsets = nullptr;
-  R.names_bytes = 0;
-  R.rows = R.cols = R.indptr = R.indices = R.data = nullptr;
-  if (D.err_detail) R.err_detail = (const uint8_t*)download(c, H->detail, D.err_detail, (size_t)D.err_detail_len);
-  G2N_HIP(hipStreamSynchronize(c->stream));
-}
-
-// The graph path's ASCII decode of node keys after a clean build: true (H's result then carries
-// G2N_E_UNICODE, err_line -1, the lowest such node id and its key) when a key has a byte >= 0x80.
-static bool ascii_key_check(g2n_context* c, const g2n_result& D, HostResult* H) {
-  g2n_result& R = H->r;
-  if (!D.names_blob || !D.names_bytes || !D.n_nodes) return false;
-  StatsOut* so = stats_out_reset(c);
-  const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
-  hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
-  hipLaunchKernelGGL(k_high_owner, dim3(1), dim3(64), 0, c->stream, D.names_offsets, (uint64_t)D.n_nodes, so);
-  const StatsOut h = read_dev(c, so);
-  if (h.high_off == ~0ull) return false;
-  if (h.high_id < 0 || h.high_id >= D.n_nodes) throw Failure(G2N_E_DEVICE, "node keys: key lookup failed");
-  int64_t span[2];
-  G2N_HIP(hipMemcpyAsync(span, D.names_offsets + h.high_id, sizeof(span), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  R.err_detail = (const uint8_t*)download(c, H->detail, D.names_blob + span[0], (size_t)(span[1] - span[0]));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  R.err_detail_len = span[1] - span[0];
-  R.status = G2N_E_UNICODE;
-  R.err_line = -1;
-  R.err_index = h.high_id;
-  set_last_error("a node key is not ASCII (the graph path decodes node keys as ASCII)");
-  return true;
-}
-
-// A stats build's result (g2n_stats_from_path): D's CSR stays on the device, the statistics are
-// taken from it there, and H receives D's scalars — plus the one key the ASCII check objects to.
-static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, const StatsRequest& q) {
-  scalars_result(c, D, H);
-  if (D.status != G2N_OK) return;
-  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_stats_from_path: the build returned no CSR");
-  csr_stats(c, D.indptr, D.indices, D.index_width, (uint64_t)D.n_nodes, (uint64_t)D.nnz, q.directed, q.out);
-  *q.n_paths = D.n_records - D.n_edges - (int64_t)c->last_n_segs;
-  if (q.check_ascii) (void)ascii_key_check(c, D, H);
-}
-
-// A distance build's result (g2n_distances_from_path): D's CSR and names stay on the device.  The
-// names go into a key table over their own blob (ids = node ids), the request's step names are
-// looked up in it in one launch, and g2n_csr_path_distances runs on the ids.
-static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, const DistRequest& q) {
-  scalars_result(c, D, H);
-  *q.oriented = 0;
-  *q.missing_step = -1;
-  if (D.status != G2N_OK) return;
-  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_distances_from_path: the build returned no CSR");
-  const uint64_t n = (uint64_t)D.n_nodes;
-  if (n && (!D.names_blob || !D.names_offsets)) throw Failure(G2N_E_DEVICE, "g2n_distances_from_path: no names");
-  if (q.check_ascii && ascii_key_check(c, D, H)) return;
-  if (q.names_if_high && n && D.names_bytes) {
-    StatsOut* so = stats_out_reset(c);
-    const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
-    hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
-    if (read_dev(c, so).high_off != ~0ull) {
-      g2n_result& R = H->r;
-      const int64_t* offs = (const int64_t*)download(c, H->offs, D.names_offsets, (size_t)(n + 1) * sizeof(int64_t));
-      G2N_HIP(hipStreamSynchronize(c->stream));
-      R.names_blob = (const uint8_t*)download(c, H->blob, D.names_blob, (size_t)offs[n]);
-      R.names_offsets = offs;
-      R.names_bytes = D.names_bytes;
-      G2N_HIP(hipStreamSynchronize(c->stream));
-    }
-  }
-  if (q.n_steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_distances_from_path: 2^32-1 or more steps");
-  dist_check_k(q.K, q.mode);
-  struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
-  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
-  // ---- the orientation flag and the first missing source step
-  auto* flags = dget<unsigned long long>(c, S_DFLAG, 2);  // [0] oriented, [1] the first missing source step
-  G2N_HIP(hipMemsetAsync(flags, 0, 8, c->stream));
-  G2N_HIP(hipMemsetAsync(flags + 1, 0xFF, 8, c->stream));
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  if (n)
-    hipLaunchKernelGGL(k_key_oriented, dim3(std::min(grid_for(n), gcap)), dim3(256), 0, c->stream, D.names_blob,
-                       D.names_offsets, n, (uint32_t*)flags);
-  // ---- the key table over the names' own blob, and the steps looked up in it
-  uint64_t cap = 1024;
-  while (cap < 2 * n) cap *= 2;
-  auto* table = dget<KsEntry>(c, S_DKS, cap);
-  G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(KsEntry), c->stream));
-  if (n)
-    hipLaunchKernelGGL(k_ks_insert, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, D.names_blob, D.names_offsets, n,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int64_t*)nullptr, (uint64_t)0,
-                       (uint64_t)0, table, cap - 1, (uint8_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr, 1);
-  const uint64_t sbytes = (uint64_t)q.step_offs[q.n_steps];
-  auto* sblob = dget<uint8_t>(c, S_DSBLOB, sbytes + 16);
-  auto* soffs = dget<int64_t>(c, S_DSOFFS, q.n_steps + 1);
-  auto* ids = dget<uint32_t>(c, S_DIDS, q.n_steps);
-  auto* fresh = dget<uint32_t>(c, S_DCUR, q.n_steps);  // (scratch: path_distances_t takes the slot afterwards)
-  auto* dpp = dget<int64_t>(c, S_DPP, q.K + 1);
-  auto* dpn = dget<int64_t>(c, S_DPN, q.n_steps);
-  if (sbytes) G2N_HIP(hipMemcpyAsync(sblob, q.step_blob, sbytes, hipMemcpyHostToDevice, c->stream));
-  G2N_HIP(hipMemcpyAsync(soffs, q.step_offs, (q.n_steps + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  G2N_HIP(hipMemcpyAsync(dpp, q.path_ptr, (q.K + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (q.n_steps) {
-    hipLaunchKernelGGL(k_ks_lookup, dim3(grid_for(q.n_steps, 256)), dim3(256), 0, c->stream, (const uint8_t*)sblob,
-                       (const int64_t*)soffs, q.n_steps, (const KsEntry*)table, cap - 1, D.names_blob, ids, fresh);
-    hipLaunchKernelGGL(k_dist_resolved, dim3(grid_for(q.n_steps)), dim3(256), 0, c->stream, (const uint32_t*)ids,
-                       q.n_steps, q.n_source_steps, dpn, flags + 1);
-  }
-  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
-  unsigned long long h[2];
-  G2N_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  *q.oriented = (uint32_t)h[0] != 0;
-  float ms = 0.f;
-  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  if (h[1] != ~0ull) {
-    *q.missing_step = (int64_t)h[1];
-    std::memset(q.info, 0, sizeof(*q.info));
-    q.info->ms_resolve = ms;
-    return;
-  }
-  const uint64_t tbytes = dist_table_bytes(q.K, q.mode);
-  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
-  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, q.K, q.mode, dtab, q.info);
-  q.info->ms_resolve = ms;
-  if (tbytes) G2N_HIP(hipMemcpyAsync(q.tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-}
-
-// A sequence-distance build's result (g2n_seq_distance_from_path): as dist_result up to the key
-// table; then the S records of the staged input in[0, len) give the two lists of node ids
-// (g2n_seq.hip), which g2n_csr_path_distances searches as K = 2.
-static void seq_result(g2n_context* c, const g2n_result& D, HostResult* H, const SeqRequest& q, const uint8_t* in,
-                       uint64_t len) {
-  scalars_result(c, D, H);
-  *q.oriented = 0;
-  *q.dist = kDistUnreached;
-  std::memset(q.info, 0, sizeof(*q.info));
-  *q.hits = g2n_seq_hits();
-  if (D.status != G2N_OK) return;
-  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_seq_distance_from_path: the build returned no CSR");
-  const uint64_t n = (uint64_t)D.n_nodes;
-  if (n && (!D.names_blob || !D.names_offsets)) throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: no names");
-  if (q.check_ascii && ascii_key_check(c, D, H)) return;
-  if (q.names_if_high && n && D.names_bytes) {
-    StatsOut* so = stats_out_reset(c);
-    const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
-    hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
-    if (read_dev(c, so).high_off != ~0ull) {
-      g2n_result& R = H->r;
-      const int64_t* offs = (const int64_t*)download(c, H->offs, D.names_offsets, (size_t)(n + 1) * sizeof(int64_t));
-      G2N_HIP(hipStreamSynchronize(c->stream));
-      R.names_blob = (const uint8_t*)download(c, H->blob, D.names_blob, (size_t)offs[n]);
-      R.names_offsets = offs;
-      R.names_bytes = D.names_bytes;
-      G2N_HIP(hipStreamSynchronize(c->stream));
-    }
-  }
-  const uint64_t n_s = c->last_n_segs;
-  if (n_s >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "g2n_seq_distance_from_path: 2^32-1 or more S lines");
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  for (auto& x : ev.e) G2N_HIP(hipEventCreate(&x));
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  // ---- the line starts "S\t": the one pass over every byte
-  auto* st = dget<SeqState>(c, S_QSTATE, 1);
-  auto* lines = dget<uint64_t>(c, S_QLINES, n_s);
-  G2N_HIP(hipMemsetAsync(st, 0, sizeof(SeqState), c->stream));
-  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
-  if (len)
-    hipLaunchKernelGGL(k_seq_lines, dim3(std::min(grid_for((len + 15) / 16), gcap)), dim3(256), 0, c->stream, in, len,
-                       n_s, lines, st);
-  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
-  // ---- the orientation flag and the key table over the names' own blob (as dist_result)
-  auto* flag = dget<unsigned long long>(c, S_DFLAG, 2);
-  G2N_HIP(hipMemsetAsync(flag, 0, 16, c->stream));
-  if (n)
-    hipLaunchKernelGGL(k_key_oriented, dim3(std::min(grid_for(n), gcap)), dim3(256), 0, c->stream, D.names_blob,
-                       D.names_offsets, n, (uint32_t*)flag);
-  uint64_t cap = 1024;
-  while (cap < 2 * n) cap *= 2;
-  auto* table = dget<KsEntry>(c, S_DKS, cap);
-  G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(KsEntry), c->stream));
-  if (n)
-    hipLaunchKernelGGL(k_ks_insert, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, D.names_blob, D.names_offsets, n,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int64_t*)nullptr, (uint64_t)0,
-                       (uint64_t)0, table, cap - 1, (uint8_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr, 1);
-  if (read_dev(c, st).n_lines != n_s)
-    throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: the S lines found differ from the build's count");
-  // ---- the queries: one holding a tab or a newline equals no field; the bytes past the first 16
-  // are read on the device only by k_seq_compare
-  SeqQuery sq{};
-  uint64_t qoff[2] = {0, 0}, qbytes = 0;
-  for (int k = 0; k < 2; k++) {
-    const uint8_t* s = q.seq[k];
-    const uint64_t m = q.len[k];
-    const bool never = m && (std::memchr(s, '\t', m) || std::memchr(s, '\n', m));
-    sq.m[k] = never ? kSeqNoQuery : m;
-    if (never) continue;
-    if (m) std::memcpy(sq.head[k], s, (size_t)std::min<uint64_t>(m, kSeqHead));
-    if (m > kSeqHead) {
-      qoff[k] = qbytes;
-      qbytes += (m + 15) & ~15ull;
-    }
-  }
-  auto* dq = dget<uint8_t>(c, S_QBYTES, qbytes);
-  for (int k = 0; k < 2; k++)
-    if (sq.m[k] != kSeqNoQuery && sq.m[k] > kSeqHead)
-      G2N_HIP(hipMemcpyAsync(dq + qoff[k], q.seq[k], (size_t)sq.m[k], hipMemcpyHostToDevice, c->stream));
-  // ---- one lane per S line, the long candidates' remaining bytes, the node lists
-  auto* node_of = dget<uint32_t>(c, S_QNODE, n_s);
-  auto* fpos = dget<uint64_t>(c, S_QFPOS, n_s);
-  auto* flags = dget<uint32_t>(c, S_QFLAG, n_s);
-  auto* last = dget<unsigned long long>(c, S_QLAST, n);
-  auto* cand = dget<uint32_t>(c, S_QCAND, 2 * n_s);
-  auto* ids = dget<uint32_t>(c, S_QIDS, 2 * n_s);
-  G2N_HIP(hipMemsetAsync(last, 0, n * 8, c->stream));
-  SeqState h{};
-  if (n_s) {
-    hipLaunchKernelGGL(k_seq_classify, dim3(grid_for(n_s, 256)), dim3(256), 0, c->stream, in, len,
-                       (const uint64_t*)lines, n_s, (const KsEntry*)table, cap - 1, D.names_blob, n, sq, node_of, fpos,
-                       flags, last, cand, cand + n_s, st);
-    h = read_dev(c, st);
-    if (h.bad) throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: an S name is no node");
-    for (int k = 0; k < 2; k++)
-      if (sq.m[k] != kSeqNoQuery && sq.m[k] > kSeqHead && h.cand[k])
-        hipLaunchKernelGGL(k_seq_compare, dim3(std::min<unsigned>(h.cand[k], gcap)), dim3(256), 0, c->stream, in, len,
-                           (const uint8_t*)(dq + qoff[k]), sq.m[k], kSeqCand << k, (const uint32_t*)(cand + k * n_s),
-                           (uint64_t)h.cand[k], (const uint64_t*)fpos, flags);
-    hipLaunchKernelGGL(k_seq_nodes, dim3(grid_for(n_s, 256)), dim3(256), 0, c->stream, (const uint64_t*)lines, n_s,
-                       (const uint32_t*)node_of, (const uint32_t*)flags, (const unsigned long long*)last, ids, ids + n_s,
-                       st);
-    h = read_dev(c, st);
-  }
-  G2N_HIP(hipEventRecord(ev.e[2], c->stream));
-  unsigned long long oriented = 0;
-  G2N_HIP(hipMemcpyAsync(&oriented, flag, 8, hipMemcpyDeviceToHost, c->stream));
-  // ---- the two lists, ascending (the appends' order is arbitrary)
-  std::vector<uint32_t> got[2];
-  for (int k = 0; k < 2; k++) {
-    if (h.hits[k] > n_s) throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: node list overflow");
-    got[k].resize(h.hits[k]);
-    if (h.hits[k])
-      G2N_HIP(hipMemcpyAsync(got[k].data(), ids + k * n_s, (size_t)h.hits[k] * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  *q.oriented = (uint32_t)oriented != 0;
-  std::vector<int64_t> pn;
-  for (int k = 0; k < 2; k++) {
-    std::sort(got[k].begin(), got[k].end());
-    q.hits->ids[k].assign(got[k].begin(), got[k].end());
-    pn.insert(pn.end(), got[k].begin(), got[k].end());
-  }
-  float ms_scan = 0.f, ms_match = 0.f;
-  G2N_HIP(hipEventElapsedTime(&ms_scan, ev.e[0], ev.e[1]));
-  G2N_HIP(hipEventElapsedTime(&ms_match, ev.e[1], ev.e[2]));
-  q.info->n_s_lines = (int64_t)n_s;
-  q.info->n_with_seq = (int64_t)h.n_with_seq;
-  q.info->candidates_a = (int64_t)h.cand[0];
-  q.info->candidates_b = (int64_t)h.cand[1];
-  q.info->ms_scan = ms_scan;
-  q.info->ms_match = ms_match;
-  // ---- the listed nodes' keys (A's, then B's)
-  const uint64_t T = pn.size();
-  auto* dpn = dget<int64_t>(c, S_DPN, T);
-  std::vector<int64_t>& noffs = q.hits->name_offs;
-  noffs.assign(T + 1, 0);
-  if (T) {
-    auto* dlens = dget<int64_t>(c, S_QNLEN, T);
-    auto* doffs = dget<int64_t>(c, S_QNOFF, T + 1);
-    G2N_HIP(hipMemcpyAsync(dpn, pn.data(), T * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_seq_hit_lens, dim3(grid_for(T, 256)), dim3(256), 0, c->stream, (const int64_t*)dpn, T, n,
-                       D.names_offsets, dlens);
-    G2N_HIP(hipMemcpyAsync(noffs.data() + 1, dlens, T * 8, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    for (uint64_t i = 0; i < T; i++) {
-      if (noffs[i + 1] < 0 || noffs[i + 1] > D.names_bytes)
-        throw Failure(G2N_E_DEVICE, "g2n_seq_distance_from_path: key length out of range");
-      noffs[i + 1] += noffs[i];
-    }
-    const uint64_t nbytes = (uint64_t)noffs[T];
-    auto* dblob = dget<uint8_t>(c, S_QNBLOB, nbytes);
-    q.hits->names.resize(nbytes);
-    G2N_HIP(hipMemcpyAsync(doffs, noffs.data(), (T + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_seq_hit_names, dim3(grid_for(T, 256)), dim3(256), 0, c->stream, (const int64_t*)dpn, T, n,
-                       D.names_offsets, D.names_blob, (const int64_t*)doffs, dblob);
-    if (nbytes) G2N_HIP(hipMemcpyAsync(q.hits->names.data(), dblob, nbytes, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-  }
-  if (got[0].empty() || got[1].empty()) return;  // nothing to search
-  // ---- the search: K = 2, cell [0][1]
-  const int64_t pp[3] = {0, (int64_t)got[0].size(), (int64_t)pn.size()};
-  auto* dpp = dget<int64_t>(c, S_DPP, 3);
-  auto* dtab = dget<uint32_t>(c, S_DTAB, 4);
-  G2N_HIP(hipMemcpyAsync(dpp, pp, sizeof(pp), hipMemcpyHostToDevice, c->stream));
-  g2n_dist_info di;
-  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, 2, G2N_DIST_MIN, dtab, &di);
-  uint32_t tab[4];
-  G2N_HIP(hipMemcpyAsync(tab, dtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  *q.dist = tab[1];
-  q.info->levels = di.levels;
-  q.info->launches = di.launches;
-  q.info->batches = di.batches;
-  q.info->ms_bfs = di.ms_bfs;
-}
+namespace g2n {
 
 // the outputs of one host build: the matrix and names, or (a stats / distance request) scalars
 // (in: the len input bytes the build read, still staged on the device)
@@ -4070,7 +3205,7 @@ int g2n_csr_path_distances(g2n_context* ctx, const void* d_indptr, const void* d
                            void* d_out_tables, g2n_dist_info* info) {
   if (!info) return G2N_E_ARG;
   G2N_CTX_CALL(ctx, {
-    g2n::dist_check_k(K, mode);
+    g2n::check_tables("g2n_csr_path_distances", K, mode == G2N_DIST_MEAN ? 16 : 4);
     g2n::path_distances(ctx, d_indptr, d_indices, index_width, n, nnz, d_path_ptr, d_path_nodes, K, mode, d_out_tables,
                         info);
   });
@@ -4093,7 +3228,7 @@ int g2n_csr_path_distances_weighted(g2n_context* ctx, const void* d_indptr, cons
                                     g2n_wdist_info* info) {
   if (!info) return G2N_E_ARG;
   G2N_CTX_CALL(ctx, {
-    g2n::wdist_check_k(K, mode);
+    g2n::check_tables("g2n_csr_path_distances_weighted", K, mode == G2N_DIST_MEAN ? 16 : 8);
     g2n::wpath_distances(ctx, d_indptr, d_indices, index_width, d_values, n, nnz, d_path_ptr, d_path_nodes, K, mode,
                          d_out_tables, info);
   });

@@ -1,0 +1,845 @@
+// g2n_queries.hip — the queries over a finished, device-resident CSR: graph statistics
+// (g2n_csr_stats), hop distances between paths (g2n_csr_path_distances: g2n_dist.hip), weighted ones
+// (g2n_csr_path_distances_weighted: g2n_wdist.hip), and what a host build returns in place of its
+// matrix when a stats / distance / sequence-distance request is set (g2n_host.cpp).
+//
+// Part of g2n_pipeline.hip's translation unit, included where the host results begin: it uses that
+// file's arena and stream helpers (dget, read_dev, scan_excl, shared_context, download) as they are.
+#pragma once
+
+namespace g2n {
+
+// ------------------------------------------------------- what the queries share ------
+template <int N>
+struct Events {  // N events, destroyed with the scope
+  hipEvent_t e[N] = {};
+  void create() {
+    for (auto& x : e) G2N_HIP(hipEventCreate(&x));
+  }
+  ~Events() {
+    for (auto& x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+// f(indptr, indices) as int32_t or int64_t arrays
+template <class F>
+static void with_index_type(int32_t index_width, const void* indptr, const void* indices, F&& f) {
+  if (index_width == 4) f((const int32_t*)indptr, (const int32_t*)indices);
+  else f((const int64_t*)indptr, (const int64_t*)indices);
+}
+
+// A CSR's description, before anything is read; `who` is the public function the messages name.
+// ptrs_ok: the pointers the entry point needs whatever the sizes; entries_ok: those it needs when
+// there are entries; need_rows: entries without rows are refused here (a _host entry leaves that to
+// the device entry it calls, a distance call of no paths reads nothing).
+static void check_csr(const std::string& who, int32_t index_width, uint64_t n, uint64_t nnz, bool ptrs_ok,
+                      bool entries_ok, bool need_rows) {
+  if (index_width != 4 && index_width != 8) throw Failure(G2N_E_ARG, who + ": index_width must be 4 or 8");
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^31-1 or more nodes");
+  if (nnz >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more entries");
+  if (!ptrs_ok || (nnz && !entries_ok)) throw Failure(G2N_E_ARG, who + ": null array");
+  if (need_rows && n == 0 && nnz) throw Failure(G2N_E_ARG, who + ": entries without rows");
+}
+
+static void check_mode(const std::string& who, int32_t mode) {
+  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, who + ": unknown mode");
+}
+
+// the number of steps, from path_ptr's two ends (path_ptr[0] == 0; what lies between is the device's to check)
+static uint64_t path_steps(const std::string& who, int64_t first, int64_t last) {
+  if (first != 0 || last < 0) throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
+  if ((uint64_t)last >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
+  return (uint64_t)last;
+}
+
+// the same of a device path_ptr
+static uint64_t path_steps_dev(g2n_context* c, const std::string& who, const int64_t* path_ptr, uint64_t K,
+                               const int64_t* path_nodes) {
+  int64_t ends[2];
+  G2N_HIP(hipMemcpyAsync(&ends[0], path_ptr, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipMemcpyAsync(&ends[1], path_ptr + K, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  const uint64_t steps = path_steps(who, ends[0], ends[1]);
+  if (steps && !path_nodes) throw Failure(G2N_E_ARG, who + ": null array");
+  return steps;
+}
+
+// bytes of the K x K tables of one call, `cell` bytes a cell over all of them (hops: D uint32 = 4, or
+// S and C uint64 = 16; weighted: D float64 = 8, or S float64 and C uint64 = 16); 0 = past 2^63
+static uint64_t table_bytes(uint64_t K, uint64_t cell) {
+  if (K >= (1ull << 29)) return 0;
+  return K * K * cell;
+}
+
+// the K x K tables of one call (and the batch's K done words) must fit the device's free memory
+static void check_tables(const std::string& who, uint64_t K, uint64_t cell) {
+  size_t f = 0, t = 0;
+  G2N_HIP(hipMemGetInfo(&f, &t));
+  const uint64_t want = table_bytes(K, cell);
+  if ((K && !want) || want + K * 8 > f)
+    throw Failure(G2N_E_UNSUPPORTED,
+                  who + ": the K x K tables of " + std::to_string(K) + " paths exceed the device's free memory");
+}
+
+// a _host entry point's call on the shared context of `device`: lock, open the call, f(c), trim
+template <class F>
+static int host_call(int32_t device, F&& f) {
+  g2n_context* c = shared_context(device);
+  std::lock_guard<std::mutex> lk(c->mu);
+  enter_call(c);
+  G2N_HIP(hipSetDevice(c->device));
+  clear_call_state(c);
+  f(c);
+  shrink_shared(c);
+  return G2N_OK;
+}
+
+struct StagedCsr {
+  void *indptr, *indices;
+  double* values;  // null without values
+};
+
+// a host CSR on c's stream (S_STIP / S_STIX, S_WVAL when there are values)
+static StagedCsr stage_csr(g2n_context* c, const void* indptr, const void* indices, const double* values,
+                           int32_t index_width, uint64_t n, uint64_t nnz) {
+  const size_t w = (size_t)index_width;
+  StagedCsr d{dbuf(c, S_STIP, (size_t)(n + 1) * w), dbuf(c, S_STIX, (size_t)nnz * w),
+              values ? dget<double>(c, S_WVAL, nnz) : nullptr};
+  G2N_HIP(hipMemcpyAsync(d.indptr, indptr, (size_t)(n + 1) * w, hipMemcpyHostToDevice, c->stream));
+  if (nnz) G2N_HIP(hipMemcpyAsync(d.indices, indices, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
+  if (nnz && values) G2N_HIP(hipMemcpyAsync(d.values, values, (size_t)nnz * 8, hipMemcpyHostToDevice, c->stream));
+  return d;
+}
+
+// --------------------------------------------------------- graph statistics ------
+// g2n_csr_stats on c's stream (the caller holds c's lock and opened the call).
+template <class I>
+static void csr_stats_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz, bool directed,
+                        StatsOut* so, hipEvent_t* ev) {
+  auto* parent = dget<uint32_t>(c, S_STPARENT, n);
+  auto* diag = dget<uint8_t>(c, S_STDIAG, n);
+  uint32_t* colcnt = directed ? dget<uint32_t>(c, S_STCOL, n) : nullptr;
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_STLONG, long_cap);
+  const unsigned g = grid_for(n);
+  const unsigned gr = (unsigned)std::min<uint64_t>(g, (uint64_t)c->n_cu * 8);
+  // ---- degrees (this walk also queues the long rows for both walks)
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  G2N_HIP(hipMemsetAsync(diag, 0, n, c->stream));
+  if (colcnt) G2N_HIP(hipMemsetAsync(colcnt, 0, n * sizeof(uint32_t), c->stream));
+  const DegOp dop{diag, colcnt};
+  hipLaunchKernelGGL((k_rows_short<I, DegOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, dop, 1,
+                     long_rows, long_cap, so);
+  hipLaunchKernelGGL((k_rows_long<I, DegOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, dop,
+                     (const uint32_t*)long_rows, long_cap, so);
+  hipLaunchKernelGGL(k_deg_max<I>, dim3(gr), dim3(256), 0, c->stream, indptr, n, nnz, (const uint8_t*)diag,
+                     (const uint32_t*)colcnt, so);
+  G2N_HIP(hipEventRecord(ev[1], c->stream));
+  // ---- components
+  const HookOp hop{parent};
+  hipLaunchKernelGGL(k_cc_init<I>, dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, parent, so);
+  hipLaunchKernelGGL((k_rows_short<I, HookOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop, 0,
+                     long_rows, long_cap, so);
+  hipLaunchKernelGGL((k_rows_long<I, HookOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop,
+                     (const uint32_t*)long_rows, long_cap, so);
+  hipLaunchKernelGGL(k_cc_flatten, dim3(gr), dim3(256), 0, c->stream, parent, n, so);
+  G2N_HIP(hipEventRecord(ev[2], c->stream));
+}
+
+static StatsOut* stats_out_reset(g2n_context* c) {
+  auto* so = dget<StatsOut>(c, S_STOUT, 1);
+  G2N_HIP(hipMemsetAsync(so, 0, sizeof(StatsOut), c->stream));
+  G2N_HIP(hipMemsetAsync(&so->high_off, 0xFF, sizeof(so->high_off), c->stream));
+  return so;
+}
+
+static void csr_stats(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
+                      uint64_t nnz, int32_t directed, g2n_graph_stats* out) {
+  std::memset(out, 0, sizeof(*out));
+  check_csr("g2n_csr_stats", index_width, n, nnz, !n || indptr, indices, true);
+  out->n_nodes = (int64_t)n;
+  out->n_entries = (int64_t)nnz;
+  if (n == 0) return;
+  Events<3> ev;
+  ev.create();
+  StatsOut* so = stats_out_reset(c);
+  with_index_type(index_width, indptr, indices,
+                  [&](auto* ip, auto* ix) { csr_stats_t(c, ip, ix, n, nnz, directed != 0, so, ev.e); });
+  const StatsOut h = read_dev(c, so);
+  if (h.bad) throw Failure(G2N_E_ARG, "g2n_csr_stats: indptr / indices out of range");
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  out->ms_degree = ms;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+  out->ms_components = ms;
+  out->n_diag = (int64_t)h.n_diag;
+  out->n_components = (int64_t)h.n_roots;
+  out->max_degree = (int64_t)h.max_degree;
+}
+
+int csr_stats_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                   int32_t directed, int32_t device, g2n_graph_stats* out) {
+  check_csr("g2n_csr_stats_host", index_width, n, nnz, indptr, indices, false);
+  return host_call(device, [&](g2n_context* c) {
+    const StagedCsr d = stage_csr(c, indptr, indices, nullptr, index_width, n, nnz);
+    csr_stats(c, d.indptr, d.indices, index_width, n, nnz, directed, out);
+  });
+}
+
+// ------------------------------------------- path distances: what both searches share ------
+// The caller's arrays, checked whole on the device before anything is searched (values: null for
+// hops); the steps' paths into step_path and the nodes' step counts into cnt (n + 1, cleared here).
+template <class I>
+static void check_on_device(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
+                            const double* values, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
+                            const int64_t* path_nodes, uint64_t K, uint64_t steps, uint32_t* step_path, uint32_t* cnt,
+                            DistState* st) {
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+  G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
+                     indices, n, nnz, st);
+  if (values && nnz)
+    hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for(nnz), gcap)), dim3(256), 0, c->stream, values, nnz, st);
+  hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
+  if (steps)
+    hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
+                       step_path, cnt, st);
+  if (read_dev(c, st).bad)
+    throw Failure(G2N_E_ARG, who + ": indptr / indices / path_ptr / path_nodes out of range" +
+                                 (values ? ", or a value that is negative or not finite" : ""));
+}
+
+// One batch's search from the sources already in next (any: there are some), level by level — a
+// weighted search's level is its round (g2n_wdist.hip).  collect(L) launches the wide collect of
+// level L's frontier, wide(count) the two wide expansions of its count nodes, narrow(budget) the
+// one-workgroup kernel for up to budget levels; every launch is counted.  A correct search ends by
+// level n (a hop level is at most n - 1, the last improving round too), so a frontier past that, or a
+// narrow launch that did not advance within its budget, is a failure, not a reason to go on.
+// Returns the deepest level at which anything was found.
+template <class Collect, class Wide, class Narrow>
+static uint32_t run_frontier(g2n_context* c, const std::string& who, DistState* st, uint64_t n, bool any,
+                             int64_t* launches, Collect&& collect, Wide&& wide, Narrow&& narrow) {
+  uint64_t L = 0;
+  for (bool more = any; more;) {
+    if (L > n) throw Failure(G2N_E_DEVICE, who + ": did not converge in n rounds");
+    // wide: level L's frontier from next (count, n_long, pending cleared first)
+    G2N_HIP(hipMemsetAsync(st, 0, 3 * sizeof(uint32_t), c->stream));
+    collect((uint32_t)L);
+    ++*launches;
+    DistState h = read_dev(c, st);
+    if (h.count == 0) break;
+    if (h.count > kDistNarrowCap) {
+      wide(h.count);
+      *launches += 2;
+      L++;
+      continue;
+    }
+    // narrow: one workgroup carries it until it empties, overflows or has run its budget
+    for (;;) {
+      const uint32_t budget = (uint32_t)std::min<uint64_t>(kDistLevelBudget, n + 1 - L);  // (L <= n: >= 1)
+      narrow(budget);
+      ++*launches;
+      h = read_dev(c, st);
+      if (h.level <= L || h.level > L + budget) throw Failure(G2N_E_DEVICE, who + ": frontier state");
+      L = h.level;
+      if (h.pending) break;
+      if (h.count == 0) {
+        more = false;
+        break;
+      }
+      if (h.count > kDistNarrowCap) throw Failure(G2N_E_DEVICE, who + ": frontier state");
+      if (L > n) throw Failure(G2N_E_DEVICE, who + ": did not converge in n rounds");
+    }
+  }
+  const DistState h = read_dev(c, st);
+  if (h.bad) throw Failure(G2N_E_ARG, who + ": indptr / indices out of range");
+  return h.last_level;
+}
+
+// --------------------------------------------------------- path distances ------
+// g2n_csr_path_distances on c's stream (the caller holds c's lock and opened the call); tables: device.
+template <class I>
+static void path_distances_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz,
+                             const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, uint64_t steps, bool mean,
+                             void* tables, g2n_dist_info* info) {
+  const std::string who = "g2n_csr_path_distances";
+  auto* st = dget<DistState>(c, S_DSTATE, 1);
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  auto* mem_ptr = dget<uint32_t>(c, S_DMPTR, n + 1);
+  auto* cursor = dget<uint32_t>(c, S_DCUR, n + 1);
+  auto* mem_path = dget<uint32_t>(c, S_DMPATH, steps);
+  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
+  check_on_device(c, who, indptr, indices, (const double*)nullptr, n, nnz, path_ptr, path_nodes, K, steps, step_path,
+                  cnt, st);
+  // ---- membership: the steps sorted by node
+  scan_excl<uint32_t, uint32_t>(c, cnt, mem_ptr, n + 1);
+  G2N_HIP(hipMemcpyAsync(cursor, mem_ptr, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  if (steps)
+    hipLaunchKernelGGL(k_dist_fill, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
+                       (const uint32_t*)step_path, cursor, mem_path);
+  // ---- tables
+  DistAcc acc{mem_ptr, mem_path, nullptr, nullptr, nullptr, nullptr, K, 0};
+  if (mean) {
+    acc.S = (unsigned long long*)tables;
+    acc.C = acc.S + K * K;
+    G2N_HIP(hipMemsetAsync(tables, 0, K * K * 16, c->stream));
+  } else {
+    acc.D = (uint32_t*)tables;
+    acc.done = dget<unsigned long long>(c, S_DDONE, K);
+    G2N_HIP(hipMemsetAsync(tables, 0xFF, K * K * 4, c->stream));
+  }
+  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
+  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
+  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
+  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
+  std::vector<int64_t> h_ptr(K + 1);
+  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  const unsigned gn = std::min(grid_for(n), gcap);
+  int64_t launches = 0, levels = 0, batches = 0;
+  for (uint64_t base = 0; base < K; base += 64, batches++) {
+    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[std::min<uint64_t>(base + 64, K)];
+    acc.base = (uint32_t)base;
+    G2N_HIP(hipMemsetAsync(seen, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
+    if (acc.done) G2N_HIP(hipMemsetAsync(acc.done, 0, K * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+    if (s1 > s0) {
+      hipLaunchKernelGGL(k_dist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
+                         (const uint32_t*)step_path, (uint32_t)base, seen, next);
+      launches++;
+    }
+    const uint32_t last = run_frontier(
+        c, who, st, n, s1 > s0, &launches,
+        [&](uint32_t L) {
+          hipLaunchKernelGGL(k_dist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc, st);
+        },
+        [&](uint32_t count) {
+          hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
+                             indices, n, nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
+                             long_rows, long_cap, st);
+          hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
+                             nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
+                             (const uint32_t*)long_rows, long_cap, st);
+        },
+        [&](uint32_t budget) {
+          hipLaunchKernelGGL(k_dist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n, nnz, seen,
+                             next, queue, qmask, acc, st, budget);
+        });
+    levels = std::max<int64_t>(levels, last);
+  }
+  info->levels = levels;
+  info->launches = launches;
+  info->batches = batches;
+}
+
+static void path_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
+                           uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
+                           void* tables, g2n_dist_info* info) {
+  const std::string who = "g2n_csr_path_distances";
+  std::memset(info, 0, sizeof(*info));
+  check_mode(who, mode);
+  check_csr(who, index_width, n, nnz, !K || (path_ptr && tables && (!n || indptr)), !K || indices, K != 0);
+  if (K == 0) return;
+  const uint64_t steps = path_steps_dev(c, who, path_ptr, K, path_nodes);
+  Events<2> ev;
+  ev.create();
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
+    path_distances_t(c, ip, ix, n, nnz, path_ptr, path_nodes, K, steps, mode == G2N_DIST_MEAN, tables, info);
+  });
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  info->ms_bfs = ms;
+}
+
+// ------------------------------------------------ weighted path distances ------
+// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
+// tables: device.  Nothing is written to the tables before every array has passed its check.
+template <class I>
+static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
+                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
+                              uint64_t steps, bool mean, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
+  const std::string who = "g2n_csr_path_distances_weighted";
+  auto* st = dget<DistState>(c, S_DSTATE, 1);
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
+  check_on_device(c, who, indptr, indices, values, n, nnz, path_ptr, path_nodes, K, steps, step_path, cnt, st);
+  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
+  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
+  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
+  // ---- B paths a batch: B * n distances must fit what is free (and what the slot already holds)
+  uint64_t B = std::min<uint64_t>(64, K);
+  if (n) {
+    size_t f = 0, t = 0;
+    G2N_HIP(hipMemGetInfo(&f, &t));
+    const uint64_t avail = (uint64_t)f + c->bufs[S_WDIST].cap;
+    B = std::min<uint64_t>(B, avail / 10 * 8 / (n * 8));  // (the arena adds an eighth to what it is asked for)
+    if (B == 0)
+      throw Failure(G2N_E_UNSUPPORTED, who + ": the distances of one path over " + std::to_string(n) +
+                                           " nodes exceed the device's free memory");
+  }
+  auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
+  info->batch_paths = (int64_t)B;
+  // ---- tables
+  auto* D = (unsigned long long*)tables;
+  if (!mean)
+    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(K * K), gcap)), dim3(256), 0, c->stream, D, K * K,
+                       kWDistInf);
+  std::vector<int64_t> h_ptr(K + 1);
+  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  const unsigned gn = std::min(grid_for(n), gcap);
+  int64_t launches = 0, rounds = 0, batches = 0;
+  double ms_search = 0.0, ms_tables = 0.0;
+  for (uint64_t base = 0; base < K; base += B, batches++) {
+    const uint64_t nb = std::min<uint64_t>(B, K - base);
+    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[base + nb];
+    if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
+    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(n * B), gcap)), dim3(256), 0, c->stream, dist, n * B,
+                       kWDistInf);
+    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+    launches++;
+    if (s1 > s0) {
+      hipLaunchKernelGGL(k_wdist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
+                         (const uint32_t*)step_path, (uint32_t)base, (uint32_t)B, dist, next);
+      launches++;
+    }
+    // round R expands the nodes that round R - 1 improved (round 0: the sources)
+    const uint32_t last = run_frontier(
+        c, who, st, n, s1 > s0, &launches,
+        [&](uint32_t R) {
+          hipLaunchKernelGGL(k_wdist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, R, queue, qmask, st);
+        },
+        [&](uint32_t count) {
+          hipLaunchKernelGGL(k_wdist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
+                             indices, values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
+                             (const unsigned long long*)qmask, long_rows, long_cap, st);
+          hipLaunchKernelGGL(k_wdist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices,
+                             values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
+                             (const unsigned long long*)qmask, (const uint32_t*)long_rows, long_cap, st);
+        },
+        [&](uint32_t budget) {
+          hipLaunchKernelGGL(k_wdist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, values, n,
+                             nnz, (uint32_t)B, dist, next, queue, qmask, st, budget);
+        });
+    rounds = std::max<int64_t>(rounds, last);
+    // ---- the batch's rows of the tables
+    G2N_HIP(hipEventRecord(ev[1], c->stream));
+    if (mean)
+      hipLaunchKernelGGL(k_wdist_mean, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes, steps, n,
+                         K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base, (double*)tables,
+                         D + K * K);
+    else if (steps)
+      hipLaunchKernelGGL(k_wdist_min, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
+                         (const uint32_t*)step_path, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb,
+                         (uint32_t)base, D);
+    launches++;
+    G2N_HIP(hipEventRecord(ev[2], c->stream));
+    G2N_HIP(hipEventSynchronize(ev[2]));
+    float ms = 0.f;
+    G2N_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    ms_search += ms;
+    G2N_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    ms_tables += ms;
+  }
+  info->rounds = rounds;
+  info->launches = launches;
+  info->batches = batches;
+  info->ms_search = ms_search;
+  info->ms_tables = ms_tables;
+}
+
+static void wpath_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width,
+                            const double* values, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
+                            const int64_t* path_nodes, uint64_t K, int32_t mode, void* tables, g2n_wdist_info* info) {
+  const std::string who = "g2n_csr_path_distances_weighted";
+  std::memset(info, 0, sizeof(*info));
+  info->batch_paths = (int64_t)std::max<uint64_t>(1, std::min<uint64_t>(64, K));
+  check_mode(who, mode);
+  check_csr(who, index_width, n, nnz, !K || (path_ptr && tables && (!n || indptr)), !K || (indices && values), K != 0);
+  if (K == 0) return;
+  const uint64_t steps = path_steps_dev(c, who, path_ptr, K, path_nodes);
+  Events<3> ev;
+  ev.create();
+  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
+    wpath_distances_t(c, ip, ix, values, n, nnz, path_ptr, path_nodes, K, steps, mode == G2N_DIST_MEAN, tables, info,
+                      ev.e);
+  });
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// The two distance _host entries: the CSR (values: null for hops), the paths (S_DPP / S_DPN) and the
+// tables (S_DTAB, `cell` bytes a cell) on the shared context, search(c, csr, path_ptr, path_nodes,
+// tables) on them, and the tables copied back.
+template <class Search>
+static int distances_host(const std::string& who, const void* indptr, const void* indices, int32_t index_width,
+                          const double* values, bool weighted, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
+                          const int64_t* path_nodes, uint64_t K, int32_t mode, void* out_tables, int32_t device,
+                          Search&& search) {
+  check_mode(who, mode);
+  check_csr(who, index_width, n, nnz, indptr && path_ptr && (!K || out_tables), indices && (!weighted || values), false);
+  if (path_ptr[K] && !path_nodes) throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
+  const uint64_t steps = path_steps(who, path_ptr[0], path_ptr[K]);
+  const uint64_t cell = mode == G2N_DIST_MEAN ? 16 : weighted ? 8 : 4;
+  return host_call(device, [&](g2n_context* c) {
+    check_tables(who, K, cell);
+    const StagedCsr d = stage_csr(c, indptr, indices, values, index_width, n, nnz);
+    auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
+    auto* dpn = dget<int64_t>(c, S_DPN, steps);
+    const uint64_t tbytes = table_bytes(K, cell);
+    void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
+    G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
+    search(c, d, dpp, dpn, dtab);
+    if (tbytes) G2N_HIP(hipMemcpyAsync(out_tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+int csr_path_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                            const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, int32_t mode,
+                            void* out_tables, int32_t device, g2n_dist_info* info) {
+  return distances_host("g2n_csr_path_distances_host", indptr, indices, index_width, nullptr, false, n, nnz, path_ptr,
+                        path_nodes, K, mode, out_tables, device,
+                        [&](g2n_context* c, const StagedCsr& d, const int64_t* dpp, const int64_t* dpn, void* dtab) {
+                          path_distances(c, d.indptr, d.indices, index_width, n, nnz, dpp, dpn, K, mode, dtab, info);
+                        });
+}
+
+int csr_path_distances_weighted_host(const void* indptr, const void* indices, int32_t index_width, const double* values,
+                                     uint64_t n, uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes,
+                                     uint64_t K, int32_t mode, void* out_tables, int32_t device, g2n_wdist_info* info) {
+  return distances_host("g2n_csr_path_distances_weighted_host", indptr, indices, index_width, values, true, n, nnz,
+                        path_ptr, path_nodes, K, mode, out_tables, device,
+                        [&](g2n_context* c, const StagedCsr& d, const int64_t* dpp, const int64_t* dpn, void* dtab) {
+                          wpath_distances(c, d.indptr, d.indices, index_width, d.values, n, nnz, dpp, dpn, K, mode, dtab,
+                                          info);
+                        });
+}
+
+// ------------------------------------------- a host build's result for a request ------
+static thread_local const StatsRequest* t_stats_request = nullptr;
+void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
+static thread_local const DistRequest* t_dist_request = nullptr;
+void set_dist_request(const DistRequest* req) { t_dist_request = req; }
+static thread_local const SeqRequest* t_seq_request = nullptr;
+void set_seq_request(const SeqRequest* req) { t_seq_request = req; }
+
+// H's result as D's scalars, no matrix and no names (a stats or distance request's build)
+static void scalars_result(g2n_context* c, const g2n_result& D, HostResult* H) {
+  g2n_result& R = H->r;
+  std::memcpy(&R, &D, sizeof(g2n_result));
+  R.priv_ = H;
+  R.err_detail = nullptr;
+  R.names_blob = nullptr;
+  R.names_offsets = nullptr;
+  R.names_bytes = 0;
+  R.rows = R.cols = R.indptr = R.indices = R.data = nullptr;
+  if (D.err_detail) R.err_detail = (const uint8_t*)download(c, H->detail, D.err_detail, (size_t)D.err_detail_len);
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// The graph path's ASCII decode of node keys after a clean build: true (H's result then carries
+// G2N_E_UNICODE, err_line -1, the lowest such node id and its key) when a key has a byte >= 0x80.
+static bool ascii_key_check(g2n_context* c, const g2n_result& D, HostResult* H) {
+  g2n_result& R = H->r;
+  if (!D.names_blob || !D.names_bytes || !D.n_nodes) return false;
+  StatsOut* so = stats_out_reset(c);
+  const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
+  hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
+  hipLaunchKernelGGL(k_high_owner, dim3(1), dim3(64), 0, c->stream, D.names_offsets, (uint64_t)D.n_nodes, so);
+  const StatsOut h = read_dev(c, so);
+  if (h.high_off == ~0ull) return false;
+  if (h.high_id < 0 || h.high_id >= D.n_nodes) throw Failure(G2N_E_DEVICE, "node keys: key lookup failed");
+  int64_t span[2];
+  G2N_HIP(hipMemcpyAsync(span, D.names_offsets + h.high_id, sizeof(span), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  R.err_detail = (const uint8_t*)download(c, H->detail, D.names_blob + span[0], (size_t)(span[1] - span[0]));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  R.err_detail_len = span[1] - span[0];
+  R.status = G2N_E_UNICODE;
+  R.err_line = -1;
+  R.err_index = h.high_id;
+  set_last_error("a node key is not ASCII (the graph path decodes node keys as ASCII)");
+  return true;
+}
+
+// A stats build's result (g2n_stats_from_path): D's CSR stays on the device, the statistics are
+// taken from it there, and H receives D's scalars — plus the one key the ASCII check objects to.
+static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, const StatsRequest& q) {
+  scalars_result(c, D, H);
+  if (D.status != G2N_OK) return;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_stats_from_path: the build returned no CSR");
+  csr_stats(c, D.indptr, D.indices, D.index_width, (uint64_t)D.n_nodes, (uint64_t)D.nnz, q.directed, q.out);
+  *q.n_paths = D.n_records - D.n_edges - (int64_t)c->last_n_segs;
+  if (q.check_ascii) (void)ascii_key_check(c, D, H);
+}
+
+// What a distance or sequence-distance build's result begins with: H receives D's scalars; false = the
+// result is complete (the build failed, or the ASCII check objected to a key).  D's CSR and names stay
+// on the device — the names are downloaded too when names_if_high and one has a byte >= 0x80.
+static bool names_on_device(g2n_context* c, const g2n_result& D, HostResult* H, const std::string& who,
+                            bool check_ascii, bool names_if_high) {
+  scalars_result(c, D, H);
+  if (D.status != G2N_OK) return false;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, who + ": the build returned no CSR");
+  const uint64_t n = (uint64_t)D.n_nodes;
+  if (n && (!D.names_blob || !D.names_offsets)) throw Failure(G2N_E_DEVICE, who + ": no names");
+  if (check_ascii && ascii_key_check(c, D, H)) return false;
+  if (names_if_high && n && D.names_bytes) {
+    StatsOut* so = stats_out_reset(c);
+    const unsigned g = (unsigned)std::min<uint64_t>(grid_for((D.names_bytes + 15) / 16), (uint64_t)c->n_cu * 8);
+    hipLaunchKernelGGL(k_high_byte, dim3(g), dim3(256), 0, c->stream, D.names_blob, (uint64_t)D.names_bytes, so);
+    if (read_dev(c, so).high_off != ~0ull) {
+      g2n_result& R = H->r;
+      const int64_t* offs = (const int64_t*)download(c, H->offs, D.names_offsets, (size_t)(n + 1) * sizeof(int64_t));
+      G2N_HIP(hipStreamSynchronize(c->stream));
+      R.names_blob = (const uint8_t*)download(c, H->blob, D.names_blob, (size_t)offs[n]);
+      R.names_offsets = offs;
+      R.names_bytes = D.names_bytes;
+      G2N_HIP(hipStreamSynchronize(c->stream));
+    }
+  }
+  return true;
+}
+
+struct NameTable {
+  const KsEntry* table;  // over the names' own blob: ids = node ids
+  uint64_t mask;
+  unsigned long long* flags;  // S_DFLAG, two words: [0] becomes non-zero when a key is oriented, [1] the caller's
+};
+
+// the orientation flag and the key table over the names' own blob, launched on c's stream
+static NameTable name_table(g2n_context* c, const g2n_result& D) {
+  const uint64_t n = (uint64_t)D.n_nodes;
+  auto* flags = dget<unsigned long long>(c, S_DFLAG, 2);
+  G2N_HIP(hipMemsetAsync(flags, 0, 8, c->stream));
+  if (n)
+    hipLaunchKernelGGL(k_key_oriented, dim3(std::min(grid_for(n), (unsigned)c->n_cu * 8)), dim3(256), 0, c->stream,
+                       D.names_blob, D.names_offsets, n, (uint32_t*)flags);
+  uint64_t cap = 1024;
+  while (cap < 2 * n) cap *= 2;
+  auto* table = dget<KsEntry>(c, S_DKS, cap);
+  G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(KsEntry), c->stream));
+  if (n)
+    hipLaunchKernelGGL(k_ks_insert, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, D.names_blob, D.names_offsets, n,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int64_t*)nullptr, (uint64_t)0,
+                       (uint64_t)0, table, cap - 1, (uint8_t*)nullptr, (int64_t*)nullptr, (uint32_t*)nullptr, 1);
+  return {table, cap - 1, flags};
+}
+
+// A distance build's result (g2n_distances_from_path): the names go into a key table over their own
+// blob, the request's step names are looked up in it in one launch, and g2n_csr_path_distances runs
+// on the ids.
+static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, const DistRequest& q) {
+  const std::string who = "g2n_distances_from_path";
+  *q.oriented = 0;
+  *q.missing_step = -1;
+  if (!names_on_device(c, D, H, who, q.check_ascii, q.names_if_high)) return;
+  const uint64_t n = (uint64_t)D.n_nodes;
+  if (q.n_steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
+  const uint64_t cell = q.mode == G2N_DIST_MEAN ? 16 : 4;
+  check_tables(who, q.K, cell);
+  Events<2> ev;
+  ev.create();
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  // ---- the orientation flag, the key table, and the steps looked up in it
+  const NameTable nt = name_table(c, D);
+  G2N_HIP(hipMemsetAsync(nt.flags + 1, 0xFF, 8, c->stream));  // the first missing source step
+  const uint64_t sbytes = (uint64_t)q.step_offs[q.n_steps];
+  auto* sblob = dget<uint8_t>(c, S_DSBLOB, sbytes + 16);
+  auto* soffs = dget<int64_t>(c, S_DSOFFS, q.n_steps + 1);
+  auto* ids = dget<uint32_t>(c, S_DIDS, q.n_steps);
+  auto* fresh = dget<uint32_t>(c, S_DCUR, q.n_steps);  // (scratch: path_distances_t takes the slot afterwards)
+  auto* dpp = dget<int64_t>(c, S_DPP, q.K + 1);
+  auto* dpn = dget<int64_t>(c, S_DPN, q.n_steps);
+  if (sbytes) G2N_HIP(hipMemcpyAsync(sblob, q.step_blob, sbytes, hipMemcpyHostToDevice, c->stream));
+  G2N_HIP(hipMemcpyAsync(soffs, q.step_offs, (q.n_steps + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  G2N_HIP(hipMemcpyAsync(dpp, q.path_ptr, (q.K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (q.n_steps) {
+    hipLaunchKernelGGL(k_ks_lookup, dim3(grid_for(q.n_steps, 256)), dim3(256), 0, c->stream, (const uint8_t*)sblob,
+                       (const int64_t*)soffs, q.n_steps, nt.table, nt.mask, D.names_blob, ids, fresh);
+    hipLaunchKernelGGL(k_dist_resolved, dim3(grid_for(q.n_steps)), dim3(256), 0, c->stream, (const uint32_t*)ids,
+                       q.n_steps, q.n_source_steps, dpn, nt.flags + 1);
+  }
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  unsigned long long h[2];
+  G2N_HIP(hipMemcpyAsync(h, nt.flags, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *q.oriented = (uint32_t)h[0] != 0;
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  if (h[1] != ~0ull) {
+    *q.missing_step = (int64_t)h[1];
+    std::memset(q.info, 0, sizeof(*q.info));
+    q.info->ms_resolve = ms;
+    return;
+  }
+  const uint64_t tbytes = table_bytes(q.K, cell);
+  void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
+  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, q.K, q.mode, dtab, q.info);
+  q.info->ms_resolve = ms;
+  if (tbytes) G2N_HIP(hipMemcpyAsync(q.tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// A sequence-distance build's result (g2n_seq_distance_from_path): the S records of the staged
+// input in[0, len) give the two lists of node ids (g2n_seq.hip), their names looked up in the key
+// table, and g2n_csr_path_distances searches the lists as K = 2.
+static void seq_result(g2n_context* c, const g2n_result& D, HostResult* H, const SeqRequest& q, const uint8_t* in,
+                       uint64_t len) {
+  const std::string who = "g2n_seq_distance_from_path";
+  *q.oriented = 0;
+  *q.dist = kDistUnreached;
+  std::memset(q.info, 0, sizeof(*q.info));
+  *q.hits = g2n_seq_hits();
+  if (!names_on_device(c, D, H, who, q.check_ascii, q.names_if_high)) return;
+  const uint64_t n = (uint64_t)D.n_nodes;
+  const uint64_t n_s = c->last_n_segs;
+  if (n_s >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more S lines");
+  Events<3> ev;
+  ev.create();
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  // ---- the line starts "S\t": the one pass over every byte
+  auto* st = dget<SeqState>(c, S_QSTATE, 1);
+  auto* lines = dget<uint64_t>(c, S_QLINES, n_s);
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(SeqState), c->stream));
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  if (len)
+    hipLaunchKernelGGL(k_seq_lines, dim3(std::min(grid_for((len + 15) / 16), gcap)), dim3(256), 0, c->stream, in, len,
+                       n_s, lines, st);
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  const NameTable nt = name_table(c, D);
+  if (read_dev(c, st).n_lines != n_s)
+    throw Failure(G2N_E_DEVICE, who + ": the S lines found differ from the build's count");
+  // ---- the queries: one holding a tab or a newline equals no field; the bytes past the first 16
+  // are read on the device only by k_seq_compare
+  SeqQuery sq{};
+  uint64_t qoff[2] = {0, 0}, qbytes = 0;
+  for (int k = 0; k < 2; k++) {
+    const uint8_t* s = q.seq[k];
+    const uint64_t m = q.len[k];
+    const bool never = m && (std::memchr(s, '\t', m) || std::memchr(s, '\n', m));
+    sq.m[k] = never ? kSeqNoQuery : m;
+    if (never) continue;
+    if (m) std::memcpy(sq.head[k], s, (size_t)std::min<uint64_t>(m, kSeqHead));
+    if (m > kSeqHead) {
+      qoff[k] = qbytes;
+      qbytes += (m + 15) & ~15ull;
+    }
+  }
+  auto* dq = dget<uint8_t>(c, S_QBYTES, qbytes);
+  for (int k = 0; k < 2; k++)
+    if (sq.m[k] != kSeqNoQuery && sq.m[k] > kSeqHead)
+      G2N_HIP(hipMemcpyAsync(dq + qoff[k], q.seq[k], (size_t)sq.m[k], hipMemcpyHostToDevice, c->stream));
+  // ---- one lane per S line, the long candidates' remaining bytes, the node lists
+  auto* node_of = dget<uint32_t>(c, S_QNODE, n_s);
+  auto* fpos = dget<uint64_t>(c, S_QFPOS, n_s);
+  auto* flags = dget<uint32_t>(c, S_QFLAG, n_s);
+  auto* last = dget<unsigned long long>(c, S_QLAST, n);
+  auto* cand = dget<uint32_t>(c, S_QCAND, 2 * n_s);
+  auto* ids = dget<uint32_t>(c, S_QIDS, 2 * n_s);
+  G2N_HIP(hipMemsetAsync(last, 0, n * 8, c->stream));
+  SeqState h{};
+  if (n_s) {
+    hipLaunchKernelGGL(k_seq_classify, dim3(grid_for(n_s, 256)), dim3(256), 0, c->stream, in, len,
+                       (const uint64_t*)lines, n_s, nt.table, nt.mask, D.names_blob, n, sq, node_of, fpos, flags, last,
+                       cand, cand + n_s, st);
+    h = read_dev(c, st);
+    if (h.bad) throw Failure(G2N_E_DEVICE, who + ": an S name is no node");
+    for (int k = 0; k < 2; k++)
+      if (sq.m[k] != kSeqNoQuery && sq.m[k] > kSeqHead && h.cand[k])
+        hipLaunchKernelGGL(k_seq_compare, dim3(std::min<unsigned>(h.cand[k], gcap)), dim3(256), 0, c->stream, in, len,
+                           (const uint8_t*)(dq + qoff[k]), sq.m[k], kSeqCand << k, (const uint32_t*)(cand + k * n_s),
+                           (uint64_t)h.cand[k], (const uint64_t*)fpos, flags);
+    hipLaunchKernelGGL(k_seq_nodes, dim3(grid_for(n_s, 256)), dim3(256), 0, c->stream, (const uint64_t*)lines, n_s,
+                       (const uint32_t*)node_of, (const uint32_t*)flags, (const unsigned long long*)last, ids, ids + n_s,
+                       st);
+    h = read_dev(c, st);
+  }
+  G2N_HIP(hipEventRecord(ev.e[2], c->stream));
+  unsigned long long oriented = 0;
+  G2N_HIP(hipMemcpyAsync(&oriented, nt.flags, 8, hipMemcpyDeviceToHost, c->stream));
+  // ---- the two lists, ascending (the appends' order is arbitrary)
+  std::vector<uint32_t> got[2];
+  for (int k = 0; k < 2; k++) {
+    if (h.hits[k] > n_s) throw Failure(G2N_E_DEVICE, who + ": node list overflow");
+    got[k].resize(h.hits[k]);
+    if (h.hits[k])
+      G2N_HIP(hipMemcpyAsync(got[k].data(), ids + k * n_s, (size_t)h.hits[k] * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *q.oriented = (uint32_t)oriented != 0;
+  std::vector<int64_t> pn;
+  for (int k = 0; k < 2; k++) {
+    std::sort(got[k].begin(), got[k].end());
+    q.hits->ids[k].assign(got[k].begin(), got[k].end());
+    pn.insert(pn.end(), got[k].begin(), got[k].end());
+  }
+  float ms_scan = 0.f, ms_match = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms_scan, ev.e[0], ev.e[1]));
+  G2N_HIP(hipEventElapsedTime(&ms_match, ev.e[1], ev.e[2]));
+  q.info->n_s_lines = (int64_t)n_s;
+  q.info->n_with_seq = (int64_t)h.n_with_seq;
+  q.info->candidates_a = (int64_t)h.cand[0];
+  q.info->candidates_b = (int64_t)h.cand[1];
+  q.info->ms_scan = ms_scan;
+  q.info->ms_match = ms_match;
+  // ---- the listed nodes' keys (A's, then B's)
+  const uint64_t T = pn.size();
+  auto* dpn = dget<int64_t>(c, S_DPN, T);
+  std::vector<int64_t>& noffs = q.hits->name_offs;
+  noffs.assign(T + 1, 0);
+  if (T) {
+    auto* dlens = dget<int64_t>(c, S_QNLEN, T);
+    auto* doffs = dget<int64_t>(c, S_QNOFF, T + 1);
+    G2N_HIP(hipMemcpyAsync(dpn, pn.data(), T * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_seq_hit_lens, dim3(grid_for(T, 256)), dim3(256), 0, c->stream, (const int64_t*)dpn, T, n,
+                       D.names_offsets, dlens);
+    G2N_HIP(hipMemcpyAsync(noffs.data() + 1, dlens, T * 8, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < T; i++) {
+      if (noffs[i + 1] < 0 || noffs[i + 1] > D.names_bytes) throw Failure(G2N_E_DEVICE, who + ": key length out of range");
+      noffs[i + 1] += noffs[i];
+    }
+    const uint64_t nbytes = (uint64_t)noffs[T];
+    auto* dblob = dget<uint8_t>(c, S_QNBLOB, nbytes);
+    q.hits->names.resize(nbytes);
+    G2N_HIP(hipMemcpyAsync(doffs, noffs.data(), (T + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_seq_hit_names, dim3(grid_for(T, 256)), dim3(256), 0, c->stream, (const int64_t*)dpn, T, n,
+                       D.names_offsets, D.names_blob, (const int64_t*)doffs, dblob);
+    if (nbytes) G2N_HIP(hipMemcpyAsync(q.hits->names.data(), dblob, nbytes, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+  }
+  if (got[0].empty() || got[1].empty()) return;  // nothing to search
+  // ---- the search: K = 2, cell [0][1]
+  const int64_t pp[3] = {0, (int64_t)got[0].size(), (int64_t)pn.size()};
+  auto* dpp = dget<int64_t>(c, S_DPP, 3);
+  auto* dtab = dget<uint32_t>(c, S_DTAB, 4);
+  G2N_HIP(hipMemcpyAsync(dpp, pp, sizeof(pp), hipMemcpyHostToDevice, c->stream));
+  g2n_dist_info di;
+  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, 2, G2N_DIST_MIN, dtab, &di);
+  uint32_t tab[4];
+  G2N_HIP(hipMemcpyAsync(tab, dtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *q.dist = tab[1];
+  q.info->levels = di.levels;
+  q.info->launches = di.launches;
+  q.info->batches = di.batches;
+  q.info->ms_bfs = di.ms_bfs;
+}
+
+}  // namespace g2n

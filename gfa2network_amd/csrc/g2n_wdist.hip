@@ -25,10 +25,11 @@
 //   wide    k_wdist_collect (every non-zero word of next is taken and queued), k_wdist_expand /
 //           k_wdist_expand_long (a row past kStatsShortRow entries by a block).
 //   narrow  k_wdist_narrow: at most kDistNarrowCap queued nodes — ONE workgroup carries the search
-//           from round to round with both queues in LDS, for up to kWDistRoundBudget rounds a
+//           from round to round with both queues in LDS, for up to kDistLevelBudget rounds a
 //           launch; it leaves when the frontier empties, when a queue would overflow (after the
 //           round's expansion: dist / next are complete, the wide collect rebuilds the frontier
 //           from next) or when the budget is spent (the frontier goes back to queue / qmask).
+//   Both regimes are g2n_dist.hip's frontier_* templates with this file's row bodies.
 //   No workgroup waits on another; every loop runs over a row, a queue, a mask's bits or a budget.
 // Tables, once a batch has converged: D[i][j] = min over the steps of j (atomicMin on the bit
 //   patterns, one thread per step: the minimum does not depend on the order); S[i][j] / C[i][j] by
@@ -44,7 +45,6 @@
 namespace g2n {
 
 constexpr unsigned long long kWDistInf = 0x7FF0000000000000ull;  // +inf: not reached
-constexpr uint32_t kWDistRoundBudget = 8192;                     // rounds one k_wdist_narrow launch may run
 
 // every value finite and >= 0 (-0.0 is 0): one pass, before anything is searched
 __global__ void __launch_bounds__(256) k_wdist_values(const double* __restrict__ values, uint64_t nnz, DistState* st) {
@@ -81,20 +81,7 @@ __global__ void __launch_bounds__(256) k_wdist_sources(const int64_t* __restrict
 __global__ void __launch_bounds__(256) k_wdist_collect(unsigned long long* __restrict__ next, uint64_t n, uint32_t R,
                                                        uint32_t* __restrict__ queue,
                                                        unsigned long long* __restrict__ qmask, DistState* st) {
-  const uint64_t stride = (uint64_t)gridDim.x * 256;
-  for (uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += stride) {
-    if (!mask_ld(next + v)) continue;
-    const unsigned long long m = atomicExch(next + v, 0ull);
-    if (!m) continue;
-    const uint32_t k = atomicAdd(&st->count, 1u);
-    if (k >= n) continue;  // (cannot be: a node is taken once)
-    queue[k] = (uint32_t)v;
-    qmask[k] = m;
-    if (k == 0) {
-      st->level = R;
-      st->last_level = R;
-    }
-  }
+  frontier_collect(next, n, R, queue, qmask, st, [](uint32_t, unsigned long long, uint32_t) {});
 }
 
 // dist[v][b] = min(dist[v][b], du + w); true when it improved (strictly)
@@ -137,23 +124,11 @@ __global__ void __launch_bounds__(256) k_wdist_expand(const I* __restrict__ indp
                                                       const unsigned long long* __restrict__ qmask,
                                                       uint32_t* __restrict__ long_rows, uint64_t long_cap,
                                                       DistState* st) {
-  uint64_t count = st->count;
-  if (count > n) count = n;
-  const uint64_t stride = (uint64_t)gridDim.x * 256;
-  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < count; k += stride) {
-    const uint64_t u = queue[k];
-    if (u >= n) continue;
-    uint64_t b, e;
-    if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;
-    if (e - b > kStatsShortRow) {
-      const uint32_t w = atomicAdd(&st->n_long, 1u);
-      if (w < long_cap) long_rows[w] = (uint32_t)k;
-      else st->bad = 1u;
-      continue;
-    }
-    wdist_row(indices, values, n, b, e, u, qmask[k], B, dist, st,
-              [&](uint64_t c, uint32_t bit) { atomicOr(next + c, 1ull << bit); });
-  }
+  frontier_expand(indptr, n, nnz, queue, qmask, long_rows, long_cap, st,
+                  [&](uint64_t u, uint64_t b, uint64_t e, unsigned long long m) {
+                    wdist_row(indices, values, n, b, e, u, m, B, dist, st,
+                              [&](uint64_t c, uint32_t bit) { atomicOr(next + c, 1ull << bit); });
+                  });
 }
 
 // a long row by the block: u's distances once into LDS, then an entry per thread and every bit of m
@@ -195,25 +170,15 @@ __global__ void __launch_bounds__(256) k_wdist_expand_long(const I* __restrict__
                                                            const uint32_t* __restrict__ long_rows, uint64_t long_cap,
                                                            DistState* st) {
   __shared__ unsigned long long s_du[64];
-  uint64_t n_long = st->n_long, count = st->count;
-  if (n_long > long_cap) n_long = long_cap;
-  if (count > n) count = n;
-  for (uint64_t w = blockIdx.x; w < n_long; w += gridDim.x) {  // (everything up to the row is the block's: no thread leaves alone)
-    const uint64_t k = long_rows[w];
-    if (k >= count) continue;
-    const uint64_t u = queue[k];
-    if (u >= n) continue;
-    uint64_t b, e;
-    if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;
-    wdist_long_row(indices, values, n, b, e, u, qmask[k], B, dist, st, s_du, 256u,
-                   [&](uint64_t c, uint32_t bit) { atomicOr(next + c, 1ull << bit); });
-  }
+  frontier_expand_long(indptr, n, nnz, queue, qmask, long_rows, long_cap, st,
+                       [&](uint64_t u, uint64_t b, uint64_t e, unsigned long long m) {
+                         wdist_long_row(indices, values, n, b, e, u, m, B, dist, st, s_du, 256u,
+                                        [&](uint64_t c, uint32_t bit) { atomicOr(next + c, 1ull << bit); });
+                       });
 }
 
-// narrow: one workgroup, from the collected frontier in queue / qmask (st->count <= kDistNarrowCap
-// nodes of round st->level) until the frontier empties (count = 0), a queue would overflow (pending
-// = 1: next holds round `level`'s frontier, uncollected) or `budget` rounds have run (the frontier
-// is written back to queue / qmask).
+// narrow (frontier_narrow, g2n_dist.hip): a level is a round; a queued node is one whose distance
+// improved for some path, so nothing is accumulated when its word is taken
 template <class I>
 __global__ void __launch_bounds__(kDistNarrowTPB) k_wdist_narrow(const I* __restrict__ indptr,
                                                                  const I* __restrict__ indices,
@@ -224,97 +189,17 @@ __global__ void __launch_bounds__(kDistNarrowTPB) k_wdist_narrow(const I* __rest
                                                                  uint32_t* __restrict__ queue,
                                                                  unsigned long long* __restrict__ qmask, DistState* st,
                                                                  uint32_t budget) {
-  __shared__ unsigned long long qm[2][kDistNarrowCap];
-  __shared__ uint32_t qv[2][kDistNarrowCap];
-  __shared__ uint32_t s_long[kDistNarrowCap];  // frontier slots whose row the whole block walks
   __shared__ unsigned long long s_du[64];
-  __shared__ uint32_t s_cnt[2], s_nlong, s_over;
-  const uint32_t tid = threadIdx.x;
-  uint32_t cnt = st->count, R = st->level, cur = 0;
-  if (cnt > kDistNarrowCap || budget == 0) return;  // (the host launches it only below the cap)
-  for (uint32_t k = tid; k < cnt; k += kDistNarrowTPB) {
-    qv[0][k] = queue[k];
-    qm[0][k] = qmask[k];
-  }
-  if (tid == 0) {
-    s_cnt[0] = s_cnt[1] = 0;
-    s_nlong = 0;
-    s_over = 0;
-  }
-  __syncthreads();
-  for (uint32_t it = 0;; it++) {
-    const uint32_t nx = cur ^ 1u;
-    // the thread that finds next[c] zero queues c (one per node and round)
-    auto improved = [&](uint64_t c, uint32_t bit) {
-      if (atomicOr(next + c, 1ull << bit)) return;
-      const uint32_t p = atomicAdd(&s_cnt[nx], 1u);
-      if (p < kDistNarrowCap) qv[nx][p] = (uint32_t)c;
-      else s_over = 1u;
-    };
-    // ---- expand round R's frontier: short rows by a thread each, longer ones by the block
-    for (uint32_t k = tid; k < cnt; k += kDistNarrowTPB) {
-      const uint64_t u = qv[cur][k];
-      uint64_t b, e;
-      if (u >= n || !dist_row(indptr, u, nnz, &b, &e, st)) continue;
-      if (e - b > kStatsShortRow) {
-        s_long[atomicAdd(&s_nlong, 1u)] = k;  // (at most cnt <= kDistNarrowCap of them)
-        continue;
-      }
-      wdist_row(indices, values, n, b, e, u, qm[cur][k], B, dist, st, improved);
-    }
-    __syncthreads();
-    const uint32_t nl = s_nlong;
-    for (uint32_t w = 0; w < nl; w++) {
-      const uint32_t k = s_long[w];
-      const uint64_t u = qv[cur][k];
-      uint64_t b, e;
-      if (!dist_row(indptr, u, nnz, &b, &e, st)) continue;  // (the same answer in every thread)
-      wdist_long_row(indices, values, n, b, e, u, qm[cur][k], B, dist, st, s_du, kDistNarrowTPB, improved);
-    }
-    __syncthreads();
-    // every atomic of the round has returned: dist / next are complete for round R + 1
-    const uint32_t ncnt = s_cnt[nx], over = s_over;
-    R++;
-    if (over) {
-      if (tid == 0) {
-        st->count = 0;
-        st->pending = 1u;
-        st->level = R;
-      }
-      return;
-    }
-    if (ncnt == 0) {
-      if (tid == 0) {
-        st->count = 0;
-        st->pending = 0;
-        st->level = R;
-        st->last_level = R - 1;
-      }
-      return;
-    }
-    // ---- collect round R + 1: take each queued node's word
-    for (uint32_t k = tid; k < ncnt; k += kDistNarrowTPB) qm[nx][k] = atomicExch(next + qv[nx][k], 0ull);
-    if (tid == 0) {
-      s_cnt[cur] = 0;
-      s_nlong = 0;
-    }
-    __syncthreads();
-    cur = nx;
-    cnt = ncnt;
-    if (it + 1 >= budget) {
-      for (uint32_t k = tid; k < cnt; k += kDistNarrowTPB) {
-        queue[k] = qv[cur][k];
-        qmask[k] = qm[cur][k];
-      }
-      if (tid == 0) {
-        st->count = cnt;
-        st->pending = 0;
-        st->level = R;
-        st->last_level = R;
-      }
-      return;
-    }
-  }
+  frontier_narrow(
+      indptr, n, nnz, next, queue, qmask, st, budget,
+      [&](uint64_t u, uint64_t b, uint64_t e, unsigned long long m, auto& push) {
+        wdist_row(indices, values, n, b, e, u, m, B, dist, st, [&](uint64_t c, uint32_t bit) { push(c, 1ull << bit); });
+      },
+      [&](uint64_t u, uint64_t b, uint64_t e, unsigned long long m, auto& push) {
+        wdist_long_row(indices, values, n, b, e, u, m, B, dist, st, s_du, kDistNarrowTPB,
+                       [&](uint64_t c, uint32_t bit) { push(c, 1ull << bit); });
+      },
+      [](uint32_t, unsigned long long, uint32_t) {});
 }
 
 // min, after the batch's nb <= B searches have converged: step s of path j lowers D[base + b][j] to
