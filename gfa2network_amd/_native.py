@@ -64,6 +64,7 @@ TEST_NO_DIRECT = 4096    # never the direct-address tier: the lean hash tier ins
 TEST_NO_EXT_LEAN = 8192  # bidirected / weighted decimal builds through K1 + the lean parse (not tile-local)
 TEST_NO_DEC_TEXT = 16384  # edge-list export of decimal ids through the names blob (not the arithmetic render)
 TEST_NO_DEC_PREFIX = 32768  # prefixed names "P1".."PN" in S order through the direct tier (not the tile-local parse)
+TEST_NO_DIRECT_FINISH = 65536  # the MAX-SYM bucket finish staged (F1, scan, F2), never counted first and written in place
 TEST_FLAGS = int(os.environ.get("G2N_TEST_FLAGS", "0"), 0)  # (diagnostics: force the paths below for a whole run)
 # options.range_flags (include/g2n.h G2N_RANGE_*): set by the sharded / chunked protocol (shard.py)
 RANGE_DECIMAL = 1        # this byte range's ids are global decimals (range_s_base / range_n_segments)
@@ -479,6 +480,7 @@ class RawResult:
     data: np.ndarray | None = None
     sum_sorted: bool = True
     sum_buckets: bool = False  # the CSR came from the bucket partition (g2n_sym.hip), not the row sums
+    sym_direct: bool = False   # ... and its MAX-SYM finish wrote the CSR in place (k_sym_count first, no F2)
     n_cast_overflow: int = 0
     input_bytes: int = 0
     phase_ms: dict = field(default_factory=dict)
@@ -500,6 +502,7 @@ def _from_result(ptr, rc: int) -> RawResult:
     out.dtype = CODE_DTYPES.get(r.dtype, np.dtype("float64"))
     out.sum_sorted = bool(r.sum_sorted)
     out.sum_buckets = r.sum_sorted < 0
+    out.sym_direct = r.sum_t_sorted == -2
     out.n_cast_overflow = int(r.n_cast_overflow)
     out.input_bytes = int(r.input_bytes)
     if r.format == FMT_TEXT and r.data:

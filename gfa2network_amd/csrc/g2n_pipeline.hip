@@ -58,7 +58,7 @@ enum Slot {
 
 constexpr uint64_t kMinGroups = 1024;   // group slots: fewer tiles per slot until the input has about this many slots
 constexpr uint32_t kPtileSmallDiv = 4;  // partition blocks below 2^24 elements: kPartTile / this many (C2: 8 and 4 alike, 2 slower)
-constexpr uint32_t kF2Ranges = 4;       // bucket finish: F1 / F2 in this many bucket ranges, F2 of one beside F1 of the next
+constexpr uint32_t kF2Ranges = 4;       // staged bucket finish: F1 / F2 in this many bucket ranges, F2 of one beside F1 of the next
 // options.test_flags (tests only; include/g2n.h G2N_TEST_*): take a path that is normally rare, same results
 constexpr uint32_t kTestNoBuckets = G2N_TEST_NO_BUCKETS;
 constexpr uint32_t kTestNoLean = G2N_TEST_NO_LEAN;
@@ -74,6 +74,7 @@ constexpr uint32_t kTestNoDirect = G2N_TEST_NO_DIRECT;
 constexpr uint32_t kTestNoExtLean = G2N_TEST_NO_EXT_LEAN;
 constexpr uint32_t kTestNoDecText = G2N_TEST_NO_DEC_TEXT;
 constexpr uint32_t kTestNoDecPrefix = G2N_TEST_NO_DEC_PREFIX;
+constexpr uint32_t kTestNoDirectFinish = G2N_TEST_NO_DIRECT_FINISH;
 
 
 struct DevBuf {
@@ -447,10 +448,14 @@ static RowSide<T, kU> row_sums(g2n_context* c, const int32_t* rows, const int32_
 
 // Unweighted A.maximum(A.T) (sum = false) or coo.tocsr() (sum = true) through the bucket partition
 // (g2n_sym.hip): the A entries (and, for MAX-SYM, their A.T twins) are partitioned by the high bits
-// of their row (one or two hand-written passes), then one finish block per bucket writes its rows'
-// CSR entries at their final place.  False when
-// the row ids are too wide for two passes or a bucket overflowed its LDS capacity (nothing
-// usable was written: the caller runs the general path).
+// of their row (one or two hand-written passes), then one finish block per bucket merges its rows'
+// entries.  The MAX-SYM finish of a whole matrix (int32 indices, not int8) counts every bucket's
+// entries first (k_sym_count), scans the counts and has F1 write the CSR in place; the SUM CSR, a
+// sharded row slice, int8, int64 indices and a build the count pass declines stage the entries at the
+// bucket's input offset (F1), scan the counts F1 found and copy them to their place (F2), in
+// kF2Ranges bucket ranges whose F2 runs beside the next range's F1.  False when
+// the row ids are too wide for two passes, a bucket overflowed its LDS capacity or its entries
+// differed from its count (nothing usable was written: the caller runs the general path).
 // The same for a sharded build's row slice [row_base, row_base + n_rows): t_rows / t_cols / n_t =
 // the slice's A.T entries (MAX-SYM; rows = A's columns), each one element of side 1.
 template <class T>
@@ -600,12 +605,26 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
   auto* indices = dget<int32_t>(c, S_INDICES, n_el);
   T* odata = dget<T>(c, S_ODATA, n_el);
   auto* btot = dget<uint32_t>(c, S_BTOT, n_bk);
-  uint2* tmp = el == el1 ? dget<uint2>(c, S_EL1, n_el) : el1;  // the pass-1 output is dead by now
+  // The finish in place (the unweighted MAX-SYM finish of a whole matrix, int32 indices, not int8 — whose
+  // wrapping sums can drop a cell): k_sym_count gives every bucket its entry count without sorting it,
+  // one scan turns the counts into CSR offsets, and F1 writes indices, data and indptr where they belong
+  // — no staged entries, no F2, no bucket ranges.  The count pass declines on the device (ctl->sym_decline:
+  // links that mostly leave their bucket); F1 then returns at once and the staged route below runs.
+  const bool direct = !sum && !pair && n_el <= 0x7FFFFFFFull && !std::is_same<T, int8_t>::value &&
+                      !(c->test_flags & (kTestIndex64 | kTestNoDirectFinish));
   // staged entries (F1 -> F2): up to two per stored element (kElPair) — columns (u32) in tmp's 8 bytes
-  // per element, the copies (u16, written only for sums of several copies) beside them
-  auto* tcol = (uint32_t*)tmp;
-  auto* tcn = dget<uint16_t>(c, S_TCN, 2 * n_el);
-  G2N_HIP(hipMemsetAsync(&c->ctl->bucket_overflow, 0, sizeof(unsigned long long), c->stream));
+  // per element, the copies (u16, written only for sums of several copies) beside them (asked for
+  // only once the staged route runs)
+  uint32_t* tcol = nullptr;
+  uint16_t* tcn = nullptr;
+  auto staging = [&]() {
+    uint2* tmp = el == el1 ? dget<uint2>(c, S_EL1, n_el) : el1;  // the pass-1 output is dead by now
+    tcol = (uint32_t*)tmp;
+    tcn = dget<uint16_t>(c, S_TCN, 2 * n_el);
+  };
+  static_assert(offsetof(Ctl, sym_mismatch) == offsetof(Ctl, bucket_overflow) + 2 * sizeof(unsigned long long),
+                "the finish's three flags are cleared together");
+  G2N_HIP(hipMemsetAsync(&c->ctl->bucket_overflow, 0, 3 * sizeof(unsigned long long), c->stream));
 #ifdef G2N_F1_STAMPS
   unsigned long long* f1st = dget<unsigned long long>(c, S_TEMP, n_bk * kF1Stamps);
   G2N_HIP(hipMemsetAsync(f1st, 0, n_bk * kF1Stamps * 8, c->stream));
@@ -627,8 +646,46 @@ static bool csr_partition(g2n_context* c, const int32_t* rows, const int32_t* co
     auto* f1 = sum ? k_sym_finish<T, true> : k_sym_finish<T, false>;
     hipLaunchKernelGGL(f1, dim3((unsigned)nb), dim3(kFinTPB), 0, c->stream, el, (const uint32_t*)bst, (uint32_t)low,
                        n_rows, (T)1, btot, tcol, tcn, indptr, c->ctl, (uint32_t)row_base, wa, (const uint32_t*)bstA,
-                       (uint32_t)b0);
+                       (uint32_t)b0, (const uint32_t*)nullptr, (int32_t*)nullptr, (T*)nullptr);
   };
+  if (direct) {
+    boff = dget<uint32_t>(c, S_MOFF, n_bk + 1);
+    // every wave of the count pass resident at once, a bucket per wave in strides
+    static const int cnt_per_cu = [] {
+      int n = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sym_count, 64 * kCntWaves, 0) != hipSuccess || n < 1) n = 1;
+      return n;
+    }();
+    const uint64_t cnt_blocks =
+        std::min<uint64_t>((n_bk + kCntWaves - 1) / kCntWaves, (uint64_t)cnt_per_cu * (uint64_t)c->n_cu);
+    hipLaunchKernelGGL(k_sym_count, dim3((unsigned)cnt_blocks), dim3(64 * kCntWaves), 0, c->stream, el,
+                       (const uint32_t*)bst, wa, (const uint32_t*)bstA, (uint32_t)low, (uint32_t)n_bk, n_buckets, btot,
+                       c->ctl);
+    scan_excl<uint32_t, uint32_t>(c, btot, boff, n_bk);
+    hipLaunchKernelGGL((k_sym_finish<T, false, true>), dim3((unsigned)n_bk), dim3(kFinTPB), 0, c->stream, el,
+                       (const uint32_t*)bst, (uint32_t)low, n_rows, (T)1, btot, (uint32_t*)nullptr, (uint16_t*)nullptr,
+                       indptr, c->ctl, 0u, wa, (const uint32_t*)bstA, 0u, (const uint32_t*)boff, indices, odata);
+    int32_t nnz = 0;  // one wait for the three flags and the entry count
+    G2N_HIP(hipMemcpyAsync(&nnz, indptr + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    sync_ctl(c);
+#ifdef G2N_F1_STAMPS
+    stamps_to_file(c, "G2N_F1_STAMPS_OUT", f1st, n_bk * kF1Stamps);
+#endif
+    if (c->h_ctl->bucket_overflow || c->h_ctl->sym_mismatch) return false;
+    if (!c->h_ctl->sym_decline) {
+      R->format = G2N_FMT_CSR;
+      R->indptr = indptr;
+      R->nnz = (int64_t)nnz;
+      R->indices = indices;
+      R->data = odata;
+      R->sum_sorted = -1;
+      R->sum_t_sorted = -2;  // the finish in place (g2n.h)
+      phase(c, "maxsym");
+      return true;
+    }
+    // declined (F1 wrote nothing): the staged route
+  }
+  staging();
   // F2 of buckets [b0, b0 + nb) on stream st; rt[0 .. rk): the entries of the bucket ranges before them
   auto launch_f2 = [&](hipStream_t st, auto* ind, int64_t* ip64, uint64_t b0, uint64_t nb, const uint32_t* rt,
                        uint32_t rk) {

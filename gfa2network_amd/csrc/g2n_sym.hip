@@ -24,6 +24,9 @@
 //      the bucket's input offset;
 //   F2 after a scan of the buckets' entry counts, one block per bucket copies them to their CSR
 //      place (indices, data) and rebases the bucket's indptr.
+//   The unweighted MAX-SYM finish of a whole matrix needs neither the staging nor F2: a bucket's entry
+//      count follows from its pair words' keys and its few other elements without a sort (k_sym_count),
+//      so the counts are scanned first and F1 writes indices, data and indptr in place (kDirect).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -617,13 +620,145 @@ __device__ unsigned long long* g2n_f1_stamps;
   } while (0)
 #endif
 
-// F1 stages the bucket's entries (tcol / tcn) and F2 (k_sym_place) places them.
-template <class T, bool kSum>
+// The count pass of the finish in place: the entries bucket b will hold after the merge, into btot[b],
+// without sorting it.  An unweighted MAX-SYM bucket's pair words give the cells (a, b) and (b, a), both
+// inside the bucket: one bit per key (min << low | max) in a map of 2^(2 low) <= 65 536 bits, and a new
+// key counts two cells (one when a == b).  Its 8-byte elements (stream B) have their column outside
+// the bucket — pass 1 writes a pair word exactly when an entry's rows share it — so their cells
+// (row, column; the A and the A.T side of one cell merge) never meet a pair word's: counted distinct
+// among themselves.  keep() of k_sym_finish never drops a cell for bool, int32, float32 and float64,
+// so the sum is the bucket's entry count.  One wave per bucket (no block barrier), over the buckets in
+// strides, the next bucket's starts, words and first elements loaded before this one's are counted.
+// ctl->sym_decline: the build's stream B outnumbers its pair words, or one bucket holds more than
+// kFinTPB stream-B elements (each is compared with those before it) — the staged route then runs.
+constexpr uint32_t kCntWaves = 4;                                  // waves (buckets in flight) per count block
+constexpr uint32_t kCntMapWords = (1u << (2 * kSymLowMax)) / 32u;  // 2048: the key map of one wave
+constexpr uint32_t kCntQ = 4;  // 16-byte loads (8 pair words each) per lane loaded ahead: 2048 words
+constexpr uint32_t kCntBPer = kFinTPB / 64;                        // stream-B elements per lane
+
+__global__ void __launch_bounds__(64 * kCntWaves) k_sym_count(const uint2* __restrict__ el, const uint32_t* __restrict__ bstart,
+                                                             const uint16_t* __restrict__ wa, const uint32_t* __restrict__ bstA,
+                                                             uint32_t low, uint32_t n_bk, uint64_t n_buckets,
+                                                             uint32_t* __restrict__ btot, Ctl* ctl) {
+  __shared__ uint4 map4[kCntWaves][kCntMapWords / 4];
+  __shared__ unsigned long long bkey[kCntWaves][kFinTPB];
+  if (bstart[n_buckets] > bstA[n_buckets]) {  // (grid-uniform) mostly links that leave their bucket
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->sym_decline = 1;
+    return;
+  }
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t* map = (uint32_t*)map4[wv];
+  unsigned long long* bk = bkey[wv];
+  const uint32_t rmask = (1u << low) - 1u;
+  const uint32_t map_q = (((1u << (2 * low)) + 31u) / 32u + 3u) / 4u;  // uint4s of the map in use
+  const uint32_t stride = gridDim.x * kCntWaves;
+  struct Ahead {  // one bucket's loads
+    uint32_t eA, nA, eB, nB;
+    uint4 ws[kCntQ];
+    uint2 xb;
+  };
+  // the words in aligned 16-byte pieces (one load instruction per 512 words of a wave, not per 64): the
+  // pieces [q0, q0 + nq) cover the bucket's words, those outside [eA, eA + nA) are masked when counted
+  // (a piece that holds one of the array's words lies inside the array's allocation)
+  const uint4* wa4 = (const uint4*)wa;
+  auto q0_of = [](const Ahead& h) { return h.eA >> 3; };
+  auto nq_of = [](const Ahead& h) { return h.nA ? ((h.eA + h.nA + 7u) >> 3) - (h.eA >> 3) : 0u; };
+  auto starts = [&](uint32_t b, Ahead& h) {
+    h.eA = h.nA = h.eB = h.nB = 0;
+    if (b < n_bk) {
+      h.eA = bstA[b];
+      h.nA = bstA[b + 1] - h.eA;
+      h.eB = bstart[b];
+      h.nB = bstart[b + 1] - h.eB;
+    }
+  };
+  auto fetch = [&](Ahead& h) {
+    const uint32_t q0 = q0_of(h), nq = nq_of(h);
+#pragma unroll
+    for (uint32_t k = 0; k < kCntQ; k++) {
+      const uint32_t i = lane + 64u * k;
+      h.ws[k] = i < nq ? wa4[q0 + i] : make_uint4(0, 0, 0, 0);
+    }
+    h.xb = lane < h.nB ? el[h.eB + lane] : make_uint2(0, 0);
+  };
+  uint32_t b = blockIdx.x * kCntWaves + wv;
+  Ahead cur, nxt;
+  starts(b, cur);
+  fetch(cur);
+  starts(b + stride, nxt);
+  for (; b < n_bk; b += stride) {
+    Ahead n2;
+    fetch(nxt);  // the next bucket's words, and the starts of the one after, in flight
+    starts(b + 2 * stride, n2);
+    const bool over = cur.nA + cur.nB > kSymCap;  // (wave-uniform) k_sym_finish reports the overflow
+    const bool wide = cur.nB > kFinTPB;
+    if (wide && !over && lane == 0) ctl->sym_decline = 1;
+    uint32_t cells = 0;
+    if (!over && !wide) {
+      for (uint32_t i = lane; i < map_q; i += 64) map4[wv][i] = make_uint4(0, 0, 0, 0);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      auto word = [&](uint32_t w) {
+        const uint32_t ra = (w >> low) & rmask, rb = w & rmask;  // (sym_word_rows' rows inside the bucket)
+        const uint32_t lo = ra < rb ? ra : rb, hi = ra < rb ? rb : ra;
+        const uint32_t key = (lo << low) | hi, bit = 1u << (key & 31u);
+        if (!(atomicOr(&map[key >> 5], bit) & bit)) cells += lo != hi ? 2u : 1u;
+      };
+      const uint32_t q0 = q0_of(cur), nq = nq_of(cur), wend = cur.eA + cur.nA;
+      auto piece = [&](uint4 v, uint32_t q) {  // the 8 words of piece q
+        const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 8; j++) {
+          const uint32_t i = 8u * q + j;
+          if (i >= cur.eA && i < wend) word((u[j >> 1] >> (16u * (j & 1u))) & 0xFFFFu);
+        }
+      };
+#pragma unroll
+      for (uint32_t k = 0; k < kCntQ; k++)
+        if (lane + 64u * k < nq) piece(cur.ws[k], q0 + lane + 64u * k);
+      for (uint32_t i = lane + 64u * kCntQ; i < nq; i += 64) piece(wa4[q0 + i], q0 + i);
+      // stream B: element i counts unless an earlier one names its cell
+      uint2 xs[kCntBPer];
+#pragma unroll
+      for (uint32_t q = 0; q < kCntBPer; q++) {
+        const uint32_t i = lane + 64u * q;
+        xs[q] = q == 0 ? cur.xb : (i < cur.nB ? el[cur.eB + i] : make_uint2(0, 0));
+        if (i < cur.nB) bk[i] = ((unsigned long long)xs[q].x << 32) | (xs[q].y >> 2);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (uint32_t q = 0; q < kCntBPer; q++) {
+        const uint32_t i = lane + 64u * q;
+        if (i < cur.nB) {
+          const unsigned long long me = ((unsigned long long)xs[q].x << 32) | (xs[q].y >> 2);
+          bool dup = false;
+          for (uint32_t j = 0; j < i; j++) dup |= bk[j] == me;
+          cells += dup ? 0u : 1u;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();  // every read of bk before the next bucket's writes
+    }
+    for (int o = 32; o > 0; o >>= 1) cells += (uint32_t)__shfl_xor((int)cells, o, 64);
+    if (lane == 0) btot[b] = cells;
+    cur = nxt;
+    nxt = n2;
+  }
+}
+
+// F1 stages the bucket's entries (tcol / tcn) and F2 (k_sym_place) places them.  kDirect (the
+// unweighted MAX-SYM finish after k_sym_count and one scan of its counts): F1 writes indices, data
+// and the final indptr itself, at the bucket's CSR offset boff[b]; a bucket whose entries differ
+// from its count sets ctl->sym_mismatch (the build is then dropped, as after an overflow).
+template <class T, bool kSum, bool kDirect = false>
 __global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8, 8))) k_sym_finish(const uint2* __restrict__ el, const uint32_t* __restrict__ bstart,
                                                      uint32_t low, uint64_t n_rows, T one, uint32_t* __restrict__ btot,
                                                      uint32_t* __restrict__ tcol, uint16_t* __restrict__ tcn,
                                                      int32_t* __restrict__ indptr, Ctl* ctl, uint32_t row_base, const uint16_t* __restrict__ wa,
-                                                     const uint32_t* __restrict__ bstA, uint32_t b0) {
+                                                     const uint32_t* __restrict__ bstA, uint32_t b0,
+                                                     const uint32_t* __restrict__ boff, int32_t* __restrict__ indices,
+                                                     T* __restrict__ data) {
+  static_assert(!(kSum && kDirect), "the finish in place is MAX-SYM's");
   __shared__ __attribute__((aligned(16))) uint32_t seg[kSymCap];  // values (column << 1 | side) grouped by row; then merged columns
   __shared__ uint32_t cnt[kFinTPB];
   __shared__ uint32_t cur[kFinTPB];    // placement cursors
@@ -635,6 +770,12 @@ __global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8,
   cnt[threadIdx.x] = 0;
   if (threadIdx.x == 0) mcount = 0;
   const uint64_t b = b0 + blockIdx.x;  // b0: the first bucket of this launch (F1 / F2 overlapped by ranges)
+  uint32_t base = 0, given = 0;  // in place: the bucket's CSR offset and the entries k_sym_count gave it
+  if constexpr (kDirect) {
+    if (ctl->sym_decline) return;  // (grid-uniform) the count pass declined: the staged route runs instead
+    base = boff[b];
+    given = btot[b];
+  }
   // stored elements (a kElPair one is two entries): stream B's (8-byte elements) and stream A's (pair
   // words, bstA non-null); the bucket stages its entries at twice its offset in both streams together
   const uint32_t eB = bstart[b], nB = bstart[b + 1] - eB;
@@ -820,21 +961,40 @@ __global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8,
   const uint32_t m = !live ? 0u : (shortrow ? short_merge() : midrow ? mval[threadIdx.x] : long_merge(none));
   uint32_t off;
   const uint32_t tot = block_excl_scan_n<kFinTPB>(m, &off, red);
-  if (threadIdx.x == 0) btot[b] = tot;
+  if constexpr (kDirect) {  // a wrong count must never become a wrong matrix
+    if (threadIdx.x == 0 && tot != given) ctl->sym_mismatch = 1;
+  } else {
+    if (threadIdx.x == 0) btot[b] = tot;
+  }
   F1_STAMP(4);
   // tot <= nx <= 2 n: the bucket's staged entries stay inside [2 e0, 2 e0 + 2 n).  A staged entry is
   // its column with bit 31 set when its value sums more than one copy (columns < 2^30); only then
   // are the copies written (ocn), so the common single copy costs no bytes
-  uint32_t* ocol = tcol + 2 * (uint64_t)e0;
-  uint16_t* ocn = tcn + 2 * (uint64_t)e0;
-  auto stage = [&](uint32_t j, uint32_t c, uint32_t kk) -> uint32_t {  // entry j of the bucket, staged
-    if (kk > 1u) ocn[j] = (uint16_t)kk;
+  // (in place: the counts' scan keeps base + tot within the expanded elements of the buckets up to
+  // this one, whatever the counts are: a count is at most 2 nA + nB, and so is tot)
+  uint32_t* ocol = kDirect ? nullptr : tcol + 2 * (uint64_t)e0;
+  uint16_t* ocn = kDirect ? nullptr : tcn + 2 * (uint64_t)e0;
+  int32_t* oind = kDirect ? indices + base : nullptr;
+  T* odat = kDirect ? data + base : nullptr;
+  // entry j of the bucket, staged: a value of several copies is written here (in place: the value itself)
+  auto stage = [&](uint32_t j, uint32_t c, uint32_t kk) -> uint32_t {
+    if (kk > 1u) {
+      if constexpr (kDirect) odat[j] = sum_copies<T>(one, kk);
+      else ocn[j] = (uint16_t)kk;
+    }
     return kk > 1u ? (c | kMultiCopy) : c;
   };
-  auto out = [&](uint32_t j, uint32_t c, uint32_t kk) { ocol[j] = stage(j, c, kk); };  // ... straight out
+  auto out = [&](uint32_t j, uint32_t c, uint32_t kk) {  // ... straight out
+    if constexpr (kDirect) {
+      oind[j] = (int32_t)c;
+      odat[j] = sum_copies<T>(one, kk);
+    } else {
+      ocol[j] = stage(j, c, kk);
+    }
+  };
   if (live) {
-    indptr[row] = (int32_t)off;  // local: k_sym_place adds the bucket's offset
-    if (row == n_rows - 1) indptr[n_rows] = (int32_t)(off + m);
+    indptr[row] = (int32_t)(base + off);  // staged: local (base 0), k_sym_place adds the bucket's offset
+    if (row == n_rows - 1) indptr[n_rows] = (int32_t)(base + off + m);
     if (longrow)  // straight out, before the staging below reuses the segments
       long_merge([&](uint32_t j, uint32_t c, uint32_t kk) { out(off + j, c, kk); });
     if (midrow) mval[threadIdx.x] = off;
@@ -866,7 +1026,12 @@ __global__ void __launch_bounds__(kFinTPB) __attribute__((amdgpu_waves_per_eu(8,
   for (uint32_t i = threadIdx.x; i < tot; i += kFinTPB) {
     const uint32_t c = seg[i];
     if (c == kStagedSkip) continue;
-    ocol[i] = c;
+    if constexpr (kDirect) {  // (a flagged entry's value is already there: stage())
+      oind[i] = (int32_t)(c & ~kMultiCopy);
+      if (!(c & kMultiCopy)) odat[i] = one;
+    } else {
+      ocol[i] = c;
+    }
   }
 #ifdef G2N_F1_STAMPS
   F1_STAMP(6);

@@ -140,8 +140,10 @@ enum {
                                    extended tile-local parse */
   G2N_TEST_NO_DEC_TEXT = 16384, /* edge-list export of a decimal-id build through the names blob, not
                                    the arithmetic render */
-  G2N_TEST_NO_DEC_PREFIX = 32768 /* names "P1".."PN" in S order through the direct-address tier, not
+  G2N_TEST_NO_DEC_PREFIX = 32768, /* names "P1".."PN" in S order through the direct-address tier, not
                                    the tile-local decimal parse behind the prefix */
+  G2N_TEST_NO_DIRECT_FINISH = 65536 /* the MAX-SYM bucket finish through its staged route (F1, scan, F2),
+                                   never counted first and written in place */
 };
 
 #define G2N_MAX_PHASES 40
@@ -183,7 +185,9 @@ typedef struct g2n_result {
                                   RuntimeWarning("overflow encountered in cast") once each */
   uint64_t input_bytes;        /* uncompressed GFA bytes parsed */
   int32_t n_phases;            /* device phase timings (hipEvent, pipeline stream) */
-  int32_t sum_t_sorted;        /* MAX-SYM: has_sorted_indices of A.T's scattered COO (diagnostic) */
+  int32_t sum_t_sorted;        /* MAX-SYM: has_sorted_indices of A.T's scattered COO (diagnostic; -1: not
+                                  computed — the bucket partition's staged finish; -2: its finish
+                                  counted first and written in place) */
   double phase_ms[G2N_MAX_PHASES];
   const char *phase_names[G2N_MAX_PHASES];
   double host_ms_read;         /* host ingest (read / inflate) */
