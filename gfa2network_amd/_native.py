@@ -44,6 +44,7 @@ EXPORTED = [
     "g2n_csr_path_distances", "g2n_csr_path_distances_host", "g2n_load_paths", "g2n_paths_get", "g2n_paths_free",
     "g2n_distances_from_path", "g2n_csr_path_distances_weighted", "g2n_csr_path_distances_weighted_host",
     "g2n_seq_distance_from_path", "g2n_seq_hits_get", "g2n_seq_hits_names", "g2n_seq_hits_free",
+    "g2n_graph_weights_from_path", "g2n_wdistances_from_path", "g2n_seq_wdistance_from_path",
 ]
 
 
@@ -194,7 +195,7 @@ class SeqInfo(ctypes.Structure):
     ]
 
 
-DIST_MIN, DIST_MEAN = 0, 1
+DIST_MIN, DIST_MEAN, DIST_MEAN_FOLD = 0, 1, 2  # (MEAN_FOLD: the weighted searches only)
 
 _lib = None
 
@@ -383,6 +384,18 @@ def load() -> ctypes.CDLL:
                                                ctypes.POINTER(SeqInfo), ctypes.POINTER(I32),
                                                ctypes.POINTER(ctypes.POINTER(Result))]
     lib.g2n_seq_distance_from_path.restype = ctypes.c_int
+    lib.g2n_graph_weights_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options),
+                                                ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_graph_weights_from_path.restype = ctypes.c_int
+    lib.g2n_wdistances_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), P, I64, I64, I32, P,
+                                             ctypes.POINTER(WDistInfo), ctypes.POINTER(I32), ctypes.POINTER(I64),
+                                             ctypes.POINTER(I32), ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_wdistances_from_path.restype = ctypes.c_int
+    lib.g2n_seq_wdistance_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), ctypes.c_char_p, U64,
+                                                ctypes.c_char_p, U64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(P),
+                                                ctypes.POINTER(SeqInfo), ctypes.POINTER(I32), ctypes.POINTER(I32),
+                                                ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_seq_wdistance_from_path.restype = ctypes.c_int
     lib.g2n_seq_hits_get.argtypes = [P] + [P] * 4
     lib.g2n_seq_hits_get.restype = None
     lib.g2n_seq_hits_names.argtypes = [P, P, P]
@@ -624,7 +637,8 @@ def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, va
                                      device: int = 0) -> tuple[tuple, dict]:
     """g2n_csr_path_distances_weighted_host on a host CSR (indptr / indices both int32 or both int64,
     float64 values) and K paths (as csr_path_distances_host): ((D,) or (S, C), the g2n_wdist_info
-    fields) — the directed K x K tables, float64 D (inf = unreached) or float64 S and uint64 C."""
+    fields) — the directed K x K tables, float64 D (inf = unreached) or float64 S and uint64 C.
+    ``mean="fold"``: G2N_DIST_MEAN_FOLD, S above the diagonal holding the reference's running total."""
     lib = load()
     idt = np.dtype(indptr.dtype)
     if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
@@ -646,7 +660,7 @@ def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, va
     rc = lib.g2n_csr_path_distances_weighted_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize,
                                                   val.ctypes.data if val.size else None, n, len(ix), pp.ctypes.data,
                                                   pn.ctypes.data if pn.size else None, K,
-                                                  DIST_MEAN if mean else DIST_MIN,
+                                                  _wdist_mode(mean),
                                                   out.ctypes.data if out.size else None, int(device),
                                                   ctypes.byref(info))
     if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
@@ -656,9 +670,7 @@ def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, va
     if rc != OK:
         raise RuntimeError(f"{status_name(rc)}: {last_error()}")
     tabs = (out[0], out[1].view(np.uint64)) if mean else (out[0],)
-    return tabs, {"rounds": int(info.rounds), "launches": int(info.launches), "batches": int(info.batches),
-                  "batch_paths": int(info.batch_paths), "ms_search": float(info.ms_search),
-                  "ms_tables": float(info.ms_tables)}
+    return tabs, _wdist_info(info)
 
 
 class Paths:
@@ -714,6 +726,40 @@ class Paths:
             self._h = None
 
 
+def _wdist_mode(mean) -> int:
+    return DIST_MEAN_FOLD if mean == "fold" else DIST_MEAN if mean else DIST_MIN
+
+
+def _wdist_info(info: WDistInfo) -> dict:
+    return {"rounds": int(info.rounds), "launches": int(info.launches), "batches": int(info.batches),
+            "batch_paths": int(info.batch_paths), "ms_search": float(info.ms_search),
+            "ms_tables": float(info.ms_tables)}
+
+
+def graph_weights_from_path(path: str, opts: Options) -> RawResult:
+    """g2n_graph_weights_from_path: the float64 CSR of the graph a weight tag builds (opts.weight_tag)."""
+    lib = load()
+    res = ctypes.POINTER(Result)()
+    rc = lib.g2n_graph_weights_from_path(os.fsencode(path), ctypes.byref(opts), ctypes.byref(res))
+    return _from_result(res, rc)
+
+
+def wdistances_from_path(path: str, opts: Options, paths: Paths, source: int, target: int, mean):
+    """g2n_wdistances_from_path (opts.weight_tag set): as distances_from_path, with float64 tables —
+    (D,), or (S, C) for ``mean`` true (``"fold"``: G2N_DIST_MEAN_FOLD) —, the g2n_wdist_info fields
+    and, last, whether a stored weight is negative or not finite (nothing was searched then)."""
+    lib = load()
+    K = paths.n_paths if source < 0 else 2
+    out = np.zeros((2, K, K), dtype=np.float64) if mean else np.full((1, K, K), np.inf, dtype=np.float64)
+    info, oriented, missing, bad = WDistInfo(), ctypes.c_int32(0), ctypes.c_int64(-1), ctypes.c_int32(0)
+    res = ctypes.POINTER(Result)()
+    rc = lib.g2n_wdistances_from_path(os.fsencode(path), ctypes.byref(opts), paths._h, source, target,
+                                      _wdist_mode(mean), out.ctypes.data, ctypes.byref(info), ctypes.byref(oriented),
+                                      ctypes.byref(missing), ctypes.byref(bad), ctypes.byref(res))
+    tabs = (out[0], out[1].view(np.uint64)) if mean else (out[0],)
+    return _from_result(res, rc), tabs, _wdist_info(info), bool(oriented.value), int(missing.value), bool(bad.value)
+
+
 def distances_from_path(path: str, opts: Options, paths: Paths, source: int, target: int, mean: bool):
     """g2n_distances_from_path: (the build's result without a matrix, the tables — (D,) or (S, C), K x K
     for source < 0 else 2 x 2 —, the g2n_dist_info fields, the orientation flag, the first missing
@@ -731,18 +777,27 @@ def distances_from_path(path: str, opts: Options, paths: Paths, source: int, tar
     return _from_result(res, rc), tuple(out), d, bool(oriented.value), int(missing.value)
 
 
-def seq_distance_from_path(path: str, opts: Options, seq_a: bytes, seq_b: bytes):
+def seq_distance_from_path(path: str, opts: Options, seq_a: bytes, seq_b: bytes, weighted: bool = False):
     """g2n_seq_distance_from_path: (the build's result without a matrix, the distance — 0xFFFFFFFF:
     none reached or a set is empty —, [ids_a, ids_b]: the ascending int64 ids of the nodes that carry
     seq_a and seq_b, [keys_a, keys_b]: those nodes' keys as bytes, the g2n_seq_info fields, the
-    orientation flag).  All but the result are meaningful only when the status is OK."""
+    orientation flag).  All but the result are meaningful only when the status is OK.
+    ``weighted`` (opts.weight_tag set): g2n_seq_wdistance_from_path — the distance is a float (inf: none
+    reached) and a seventh value tells whether a stored weight is negative or not finite."""
     lib = load()
-    dist, info, oriented = ctypes.c_uint32(0xFFFFFFFF), SeqInfo(), ctypes.c_int32(0)
+    info, oriented, bad = SeqInfo(), ctypes.c_int32(0), ctypes.c_int32(0)
     hits, res = ctypes.c_void_p(), ctypes.POINTER(Result)()
     a, b = bytes(seq_a), bytes(seq_b)
-    rc = lib.g2n_seq_distance_from_path(os.fsencode(path), ctypes.byref(opts), a, len(a), b, len(b),
-                                        ctypes.byref(dist), ctypes.byref(hits), ctypes.byref(info),
-                                        ctypes.byref(oriented), ctypes.byref(res))
+    if weighted:
+        dist = ctypes.c_double(float("inf"))
+        rc = lib.g2n_seq_wdistance_from_path(os.fsencode(path), ctypes.byref(opts), a, len(a), b, len(b),
+                                             ctypes.byref(dist), ctypes.byref(hits), ctypes.byref(info),
+                                             ctypes.byref(oriented), ctypes.byref(bad), ctypes.byref(res))
+    else:
+        dist = ctypes.c_uint32(0xFFFFFFFF)
+        rc = lib.g2n_seq_distance_from_path(os.fsencode(path), ctypes.byref(opts), a, len(a), b, len(b),
+                                            ctypes.byref(dist), ctypes.byref(hits), ctypes.byref(info),
+                                            ctypes.byref(oriented), ctypes.byref(res))
     ids = [np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)]
     keys: list[list[bytes]] = [[], []]
     if hits:
@@ -763,6 +818,8 @@ def seq_distance_from_path(path: str, opts: Options, seq_a: bytes, seq_b: bytes)
         finally:
             lib.g2n_seq_hits_free(hits)
     d = {f: (float if f.startswith("ms_") else int)(getattr(info, f)) for f, _t in SeqInfo._fields_}
+    if weighted:
+        return _from_result(res, rc), float(dist.value), ids, keys, d, bool(oriented.value), bool(bad.value)
     return _from_result(res, rc), int(dist.value), ids, keys, d, bool(oriented.value)
 
 

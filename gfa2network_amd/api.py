@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "load_paths", "genome_distance", "genome_distance_matrix",
+           "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
            "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
@@ -817,6 +817,24 @@ def weighted_mean_table(S: np.ndarray, C: np.ndarray) -> np.ndarray:
     return M
 
 
+def weighted_fold_table(S: np.ndarray, C: np.ndarray) -> np.ndarray:
+    """genome_distance_matrix's symmetric mean over a weighted graph from G2N_DIST_MEAN_FOLD's tables:
+    for i < j, ``S[i][j]`` is already the reference's running total of the cell (analysis.py:254-264:
+    path i's steps against path j's distances, then path j's steps against path i's), divided here by
+    ``float(C[i][j] + C[j][i])`` and written to both triangles; ``inf`` where nothing is reached, 0.0
+    on the diagonal."""
+    S, C = np.asarray(S, dtype=np.float64), np.asarray(C, dtype=np.uint64)
+    den = (C + C.T).astype(np.float64)
+    M = np.full(S.shape, np.inf, dtype=np.float64)
+    iu = np.triu_indices(len(M), 1)
+    vals = np.full(len(iu[0]), np.inf, dtype=np.float64)
+    np.divide(S[iu], den[iu], out=vals, where=den[iu] > 0)
+    M[iu] = vals
+    M.T[iu] = vals
+    np.fill_diagonal(M, 0.0)
+    return M
+
+
 def _weighted_csr(A):
     """``A`` as a CSR whose data is float64, every value finite and >= 0 (checked here, on the host):
     a CSR keeps its entries as they are stored (repeated ones are parallel edges), another format goes
@@ -1049,9 +1067,22 @@ def load_paths(path, *, raw_bytes: bool = False, device: int = 0) -> dict:
     return {k.decode("ascii"): [s.decode("ascii") for s in v] for k, v in d.items()}
 
 
-def _dist_opts(directed: bool, raw_bytes_id: bool, device: int):
+def _dist_opts(directed: bool, raw_bytes_id: bool, device: int, weight_tag=None):
     return nat.make_options(directed=directed, asymmetric=True, output=nat.OUT_CSR, want_node_names=not raw_bytes_id,
-                            device=device)
+                            device=device, weight_tag=weight_tag or None)
+
+
+_BAD_WEIGHT = ("edge weights must be finite and >= 0 for the GPU distance search (NetworkX's result on such a graph "
+               "depends on its heap's order and is not reproduced)")
+
+
+def _paths_raw(raw: RawResult, p: str, directed: bool, raw_bytes_id: bool, device: int) -> RawResult:
+    """The build result load_paths' own pass is judged by.  load_paths parses without a weight tag, so
+    an integer tag too large for float() (builders.py:209) is the graph build's error alone: what
+    load_paths raises before it comes from a build of the same file without the tag."""
+    if raw.status != nat.E_INT_TOO_LARGE:
+        return raw
+    return nat.stats_from_path(p, _dist_opts(directed, raw_bytes_id, device))[0]
 
 
 def _missing_step(step: bytes, raw_bytes_id: bool):
@@ -1060,7 +1091,7 @@ def _missing_step(step: bytes, raw_bytes_id: bool):
 
 
 def genome_distance_matrix(gfa_path, method: str = "min", *, raw_bytes_id: bool = False, backend: str = "networkx",
-                           verbose: bool = False, device: int = 0, return_info: bool = False):
+                           verbose: bool = False, device: int = 0, return_info: bool = False, weight_tag=None):
     """GPU ``genome_distance_matrix`` (gfa2network/analysis.py:180-272): the pairwise hop distances
     between the file's P / O paths over the directed graph ``parse_gfa(gfa_path, build_graph=True)``
     builds — ``min``: the fewest hops from a step of path i to a step of path j (i < j, in both
@@ -1070,7 +1101,14 @@ def genome_distance_matrix(gfa_path, method: str = "min", *, raw_bytes_id: bool 
     the CSR and the node names stay in HBM, the step names are looked up there and one bit-parallel
     breadth-first search serves 64 paths (g2n_dist.hip); only the K x K tables come back.
     ``backend="igraph"``, stdin and file objects raise NotImplementedError.  ``device`` and
-    ``return_info`` (also return the g2n_dist_info fields) are extensions."""
+    ``return_info`` (also return the g2n_dist_info fields) are extensions.
+
+    ``weight_tag`` (extension; ``None`` or ``""``: the hop distances above, unchanged): the distances the
+    reference computes over ``parse_gfa(gfa_path, build_graph=True, weight_tag=...)`` — Dijkstra with
+    ``weight="weight"`` over the graph whose edge lengths are ``graph_matrix``'s —, bit for bit; the
+    mean is the reference's running total per cell in its order of additions.  An integer tag too
+    large for a float raises the reference's OverflowError; a stored length that is negative, NaN or
+    infinite raises NotImplementedError.  ``return_info`` then returns the g2n_wdist_info fields."""
     if backend == "igraph":
         raise NotImplementedError("backend='igraph' is outside the GPU path")
     p = _named_file(gfa_path, "genome_distance_matrix")
@@ -1079,18 +1117,26 @@ def genome_distance_matrix(gfa_path, method: str = "min", *, raw_bytes_id: bool 
     if ps.status != nat.OK:
         _unreadable(p, device)
     mean = method != "min"
-    raw, tabs, info, oriented, missing = nat.distances_from_path(p, _dist_opts(True, raw_bytes_id, device), ps, -1, -1,
-                                                                 mean)
-    _load_paths_pass(raw, ps, raw_bytes_id, gfa_path)
+    bad = False
+    if weight_tag:
+        raw, tabs, info, oriented, missing, bad = nat.wdistances_from_path(
+            p, _dist_opts(True, raw_bytes_id, device, weight_tag), ps, -1, -1, "fold" if mean else False)
+        _load_paths_pass(_paths_raw(raw, p, True, raw_bytes_id, device), ps, raw_bytes_id, gfa_path)
+    else:
+        raw, tabs, info, oriented, missing = nat.distances_from_path(p, _dist_opts(True, raw_bytes_id, device), ps, -1,
+                                                                     -1, mean)
+        _load_paths_pass(raw, ps, raw_bytes_id, gfa_path)
     names = [ps.name(k) if raw_bytes_id else ps.name(k).decode("ascii") for k in range(ps.n_paths)]
     _graph_pass(raw, raw_bytes_id, verbose, gfa_path)
     _warn_oriented(raw, oriented)
+    if bad:
+        raise NotImplementedError(_BAD_WEIGHT)
     if missing >= 0:
         raise _missing_step(ps.step(missing), raw_bytes_id)
     if mean:
-        M = mean_table(*tabs)
+        M = weighted_fold_table(*tabs) if weight_tag else mean_table(*tabs)
     else:
-        M = min_table(tabs[0])
+        M = weighted_min_table(tabs[0]) if weight_tag else min_table(tabs[0])
         iu = np.triu_indices(len(M), 1)
         M.T[iu] = M[iu]
     try:
@@ -1104,12 +1150,17 @@ def genome_distance_matrix(gfa_path, method: str = "min", *, raw_bytes_id: bool 
 
 
 def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id: bool = False,
-                    verbose: bool = False, device: int = 0):
+                    verbose: bool = False, device: int = 0, weight_tag=None):
     """``gfa2network distance GFA --path A B`` as a function (cli.py:323-346): the fewest hops from
     a step of path ``name_a`` to a step of path ``name_b`` (an int; the search runs from A only) over
     the graph ``parse_gfa(path, build_graph=True, directed=...)`` builds.  KeyError(name) for an
     unknown path name (raised before the graph is built, after load_paths' own errors),
-    NodeNotFound when a step of A is no node, NetworkXNoPath when no step of B is reached."""
+    NodeNotFound when a step of A is no node, NetworkXNoPath when no step of B is reached.
+
+    ``weight_tag`` (extension; ``None`` or ``""``: the hops above, an int, unchanged): the length of
+    the shortest path over the graph ``parse_gfa(path, build_graph=True, directed=...,
+    weight_tag=...)`` builds, as ``genome_distance_matrix`` describes — always a ``float`` (the
+    reference returns an equal ``int`` when the best path crosses untagged edges only)."""
     p = _named_file(path, "genome_distance")
     _stats_one_piece(p, device, "genome_distance", "path_distances")
     ps = nat.Paths(p)
@@ -1129,20 +1180,34 @@ def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id
         raw, _st, _n = nat.stats_from_path(p, opts)
         _load_paths_pass(raw, ps, raw_bytes_id, path)
         raise KeyError(name_a if a is None else name_b)
-    raw, tabs, _info, oriented, missing = nat.distances_from_path(p, opts, ps, a, b, False)
-    _load_paths_pass(raw, ps, raw_bytes_id, path)
+    bad = False
+    if weight_tag:
+        raw, tabs, _info, oriented, missing, bad = nat.wdistances_from_path(
+            p, _dist_opts(directed, raw_bytes_id, device, weight_tag), ps, a, b, False)
+        _load_paths_pass(_paths_raw(raw, p, directed, raw_bytes_id, device), ps, raw_bytes_id, path)
+    else:
+        raw, tabs, _info, oriented, missing = nat.distances_from_path(p, opts, ps, a, b, False)
+        _load_paths_pass(raw, ps, raw_bytes_id, path)
     _graph_pass(raw, raw_bytes_id, verbose, path)
     if directed:
         _warn_oriented(raw, oriented)
+    if bad:
+        raise NotImplementedError(_BAD_WEIGHT)
     if missing >= 0:
         raise _missing_step(ps.step(int(ps.path_ptr[a]) + missing), raw_bytes_id)
+    if weight_tag:
+        w = float(tabs[0][0, 1])
+        if w == np.inf:
+            raise NetworkXNoPath("no path between node sets")
+        return w
     d = int(tabs[0][0, 1])
     if d == 0xFFFFFFFF:
         raise NetworkXNoPath("no path between node sets")
     return d
 
 
-def _seq_pass(path, seq_a, seq_b, directed: bool, raw_bytes_id: bool, verbose: bool, device: int, who: str):
+def _seq_pass(path, seq_a, seq_b, directed: bool, raw_bytes_id: bool, verbose: bool, device: int, who: str,
+              weight_tag=None):
     """The one GPU pass of sequence_distance / sequence_nodes: the build's errors and warnings, the
     orientation warning, then KeyError for a sequence no node carries (analysis.py:103-105: repr of
     each missing argument as passed).  Returns (distance or 0xFFFFFFFF, [keys_a, keys_b], info)."""
@@ -1150,11 +1215,18 @@ def _seq_pass(path, seq_a, seq_b, directed: bool, raw_bytes_id: bool, verbose: b
     _stats_one_piece(p, device, who, "path_distances")
     a = seq_a if isinstance(seq_a, bytes) else seq_a.encode()
     b = seq_b if isinstance(seq_b, bytes) else seq_b.encode()
-    opts = _dist_opts(directed, raw_bytes_id, device)
-    raw, dist, _ids, keys, info, oriented = nat.seq_distance_from_path(p, opts, a, b)
+    bad = False
+    if weight_tag:
+        raw, dist, _ids, keys, info, oriented, bad = nat.seq_distance_from_path(
+            p, _dist_opts(directed, raw_bytes_id, device, weight_tag), a, b, weighted=True)
+    else:
+        raw, dist, _ids, keys, info, oriented = nat.seq_distance_from_path(p, _dist_opts(directed, raw_bytes_id, device),
+                                                                           a, b)
     _graph_pass(raw, raw_bytes_id, verbose, path)
     if directed:
         _warn_oriented(raw, oriented)
+    if bad:
+        raise NotImplementedError(_BAD_WEIGHT)
     missing = [repr(x) for x, k in ((seq_a, keys[0]), (seq_b, keys[1])) if not k]
     if missing:
         raise KeyError(f"sequence(s) {', '.join(missing)} not found")
@@ -1164,7 +1236,7 @@ def _seq_pass(path, seq_a, seq_b, directed: bool, raw_bytes_id: bool, verbose: b
 
 
 def sequence_distance(path, seq_a, seq_b, *, directed: bool = True, raw_bytes_id: bool = False,
-                      verbose: bool = False, device: int = 0, return_info: bool = False):
+                      verbose: bool = False, device: int = 0, return_info: bool = False, weight_tag=None):
     """``sequence_distance`` (gfa2network/analysis.py:68-113) / ``gfa2network distance GFA --seq A B``
     (cli.py:308-321) on a file where the reference takes a graph built with ``store_seq=True``: the
     fewest hops (an int) from any node whose sequence is ``seq_a`` to any node whose sequence is
@@ -1175,20 +1247,54 @@ def sequence_distance(path, seq_a, seq_b, *, directed: bool = True, raw_bytes_id
     After the build's own errors and warnings: the orientation warning on a directed graph,
     KeyError("sequence(s) 'X' not found"), NetworkXNoPath("no path between sequences").  Stdin and
     file objects raise NotImplementedError.  ``device`` and ``return_info`` (also return the
-    g2n_seq_info fields) are extensions."""
-    dist, _keys, info = _seq_pass(path, seq_a, seq_b, directed, raw_bytes_id, verbose, device, "sequence_distance")
-    if dist == 0xFFFFFFFF:
+    g2n_seq_info fields) are extensions.  ``weight_tag`` (extension; ``None`` or ``""``: the hops
+    above, unchanged): the shortest path's length, a ``float``, over the graph a weight tag builds, as
+    ``genome_distance``'s."""
+    dist, _keys, info = _seq_pass(path, seq_a, seq_b, directed, raw_bytes_id, verbose, device, "sequence_distance",
+                                  weight_tag)
+    if dist == (np.inf if weight_tag else 0xFFFFFFFF):
         raise NetworkXNoPath("no path between sequences")
     return (dist, info) if return_info else dist
 
 
-def sequence_nodes(path, seq_a, seq_b, *, directed: bool = True, raw_bytes_id: bool = False, device: int = 0):
+def sequence_nodes(path, seq_a, seq_b, *, directed: bool = True, raw_bytes_id: bool = False, device: int = 0,
+                   weight_tag=None):
     """The reference's ``seq2nodes[seq_a]``, ``seq2nodes[seq_b]`` (analysis.py:96-108) without the
     search (extension): the keys (``str``, or ``bytes`` with ``raw_bytes_id``) of the nodes that carry
     each sequence, in node order.  Errors and warnings as ``sequence_distance``'s, up to the
-    KeyError."""
+    KeyError.  ``weight_tag`` is accepted and ignored: the node sets do not depend on it."""
     _dist, keys, _info = _seq_pass(path, seq_a, seq_b, directed, raw_bytes_id, False, device, "sequence_nodes")
     return keys[0], keys[1]
+
+
+def graph_matrix(path, *, directed: bool = True, weight_tag=None, raw_bytes_id: bool = False,
+                 return_node_list: bool = False, device: int = 0):
+    """The weighted adjacency matrix of the GRAPH ``parse_gfa(path, build_graph=True, directed=...,
+    weight_tag=...)`` builds (extension), as a float64 ``scipy.sparse.csr_matrix`` with the nodes in
+    first-touch order: what ``nx.to_scipy_sparse_array(G, weight="weight", format="csr")`` gives for
+    it, and the matrix to hand to ``path_distances(A, paths, weighted=True)``.  It is not the matrix
+    ``parse_gfa(build_matrix=True, weight_tag=...)`` returns, which sums repeated records: a graph
+    edge's length is the weight of the last record of that edge carrying a numeric tag
+    (builders.py:246-256: ``add_edge`` overwrites, and sets ``weight`` only for such a record), 1.0
+    when none does; an undirected build stores both cells of an edge, an explicit 0.0 stays stored.
+    Built on the GPU in one pass over the file (g2n_graph_weights_from_path); without a tag every
+    stored value is 1.0.  Errors and the unsupported-record warning as ``parse_gfa``'s; the node
+    list as its ``return_node_list``."""
+    p = _named_file(path, "graph_matrix")
+    _stats_one_piece(p, device, "graph_matrix", "path_distances")
+    dt = np.dtype("float64")
+    if weight_tag:
+        raw = nat.graph_weights_from_path(p, nat.make_options(directed=directed, weight_tag=weight_tag,
+                                                              want_node_names=return_node_list, device=device))
+        return finalize(raw, dtype=dt, return_node_list=return_node_list, raw_bytes_id=raw_bytes_id, verbose=False,
+                        path=path)
+    raw = nat.build_from_path(p, nat.make_options(directed=directed, asymmetric=True, dtype="bool", output=nat.OUT_CSR,
+                                                  want_node_names=return_node_list, device=device))
+    out = finalize(raw, dtype=np.dtype("bool"), return_node_list=return_node_list, raw_bytes_id=raw_bytes_id,
+                   verbose=False, path=path)
+    A = out[0] if return_node_list else out
+    A = sp.csr_matrix((np.ones(A.nnz, dtype=dt), A.indices, A.indptr), shape=A.shape)
+    return (A, out[1]) if return_node_list else A
 
 
 def _run(path, opts) -> RawResult:

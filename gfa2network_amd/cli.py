@@ -5,20 +5,25 @@ gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backen
 ``convert_format``, ``save_matrix`` (dense guard -> SystemExit), then the
 ``<matrix>.nodes.tsv`` sidecar.  ``export --format edge-list`` (cli.py:264-281) renders its
 lines on the GPU from the same parse; ``stats`` (cli.py:152-159, 364-376) prints
-``compute_stats``'s six numbers, taken on the GPU from the CSR; ``distance --path`` and
-``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same CSR.
-Graph outputs (``--graph``, export graphml / gexf / json) are outside the GPU GFA->CSR path;
-``distance --seq`` is served by the function ``sequence_distance`` and not routed here yet.
+``compute_stats``'s six numbers, taken on the GPU from the CSR; ``distance --path``, ``distance
+--seq`` and ``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same
+CSR (``--seq`` finds the nodes that carry the two sequences there too: ``sequence_distance``; an input
+that is no named file is a usage error, exit status 2, where the function raises the reference's
+FileNotFoundError).  As in
+the reference, ``distance`` and ``distance-matrix`` have no ``--weight-tag``: the functions take
+``weight_tag=``.  Graph outputs (``--graph``, export graphml / gexf / json) are outside the GPU
+GFA->CSR path.
 """
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 from pathlib import Path
 
 from . import __version__
 from .api import (compute_stats, convert_format, export_edge_list, genome_distance, genome_distance_matrix, parse_gfa,
-                  parse_gfa_names, save_matrix, save_node_map_native)
+                  parse_gfa_names, save_matrix, save_node_map_native, sequence_distance)
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -106,10 +111,18 @@ def main(argv: list[str] | None = None) -> None:
     if args.cmd == "stat":
         return
     if args.cmd == "distance":  # cli.py:307-346
-        if args.seq:
-            parser.error("distance --seq is not routed here yet: call gfa2network_amd.sequence_distance(GFA, A, B)")
         if args.backend == "igraph":
             parser.error("--backend igraph is outside the GPU GFA->CSR path")
+        if args.seq:  # cli.py:308-321
+            seq_a, seq_b = args.seq
+            # sequence_distance matches the sequences in the file's staged bytes: it takes a named file,
+            # not stdin.  An input that is none is a usage error here, before a GPU is touched (the
+            # function itself raises the reference's FileNotFoundError)
+            if args.gfa == "-" or not os.path.isfile(args.gfa):
+                parser.error(f"distance --seq reads a named file (sequence_distance(GFA, A, B)): {args.gfa!r} is none")
+            print(sequence_distance(args.gfa, seq_a, seq_b, directed=args.directed, raw_bytes_id=args.raw_bytes_id,
+                                    verbose=args.verbose, device=args.device))
+            return
         name_a, name_b = args.path
         try:
             dist = genome_distance(args.gfa, name_a.encode() if args.raw_bytes_id else name_a,

@@ -14,6 +14,7 @@
 #include <new>
 #include <chrono>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -368,26 +369,47 @@ int g2n_load_paths(const char* path, g2n_paths** out) {
   });
 }
 
-int g2n_distances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
-                            int64_t target, int32_t mode, void* out_tables, g2n_dist_info* info, int32_t* oriented,
-                            int64_t* missing_step, g2n_result** res) {
-  if (!res || !path || !paths || !info || !oriented || !missing_step) return G2N_E_ARG;
+// the LAST build of the weighted from-file calls: on while the scope lives
+struct LastBuildScope {
+  explicit LastBuildScope(bool on) { g2n::set_last_build(on); }
+  ~LastBuildScope() { g2n::set_last_build(false); }
+};
+
+// the plain graph's build of the distance calls, as g2n_stats_from_path's — with the names, which the
+// steps are looked up in; weighted: the float64 LAST build over opts' weight tag
+static bool dist_build_opts(const g2n_options* opts, bool weighted, g2n_options* o) {
+  g2n_options_init(o);
+  o->directed = opts->directed != 0;
+  o->asymmetric = 1;
+  o->dtype = weighted ? G2N_FLOAT64 : G2N_BOOL;
+  o->output = G2N_OUT_CSR;
+  o->want_node_names = 1;
+  o->device = opts->device;
+  o->unknown_warned = opts->unknown_warned;
+  o->test_flags = opts->test_flags;
+  if (weighted) o->weight_tag = opts->weight_tag;
+  return !weighted || (opts->weight_tag && *opts->weight_tag);
+}
+
+// g2n_distances_from_path (info) / g2n_wdistances_from_path (winfo, bad_weight)
+static int distances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
+                               int64_t target, int32_t mode, void* out_tables, g2n_dist_info* info,
+                               g2n_wdist_info* winfo, int32_t* oriented, int64_t* missing_step, int32_t* bad_weight,
+                               g2n_result** res) {
+  if (!res || !path || !paths || (!info && !winfo) || !oriented || !missing_step || (winfo && !bad_weight))
+    return G2N_E_ARG;
   *res = nullptr;
   int rc = check_opts(opts);
   if (rc) return rc;
-  std::memset(info, 0, sizeof(*info));
+  if (info) std::memset(info, 0, sizeof(*info));
+  if (winfo) {
+    std::memset(winfo, 0, sizeof(*winfo));
+    *bad_weight = 0;
+  }
   const int64_t n_paths = (int64_t)paths->name_offs.size() - 1;
   if (source >= n_paths || (source >= 0 && (target < 0 || target >= n_paths))) return G2N_E_ARG;
-  g2n_options o;  // the plain graph's build, as g2n_stats_from_path's — with the names, which the steps are looked up in
-  g2n_options_init(&o);
-  o.directed = opts->directed != 0;
-  o.asymmetric = 1;
-  o.dtype = G2N_BOOL;
-  o.output = G2N_OUT_CSR;
-  o.want_node_names = 1;
-  o.device = opts->device;
-  o.unknown_warned = opts->unknown_warned;
-  o.test_flags = opts->test_flags;
+  g2n_options o;
+  if (!dist_build_opts(opts, winfo != nullptr, &o)) return G2N_E_ARG;
   g2n::DistRequest req{};
   std::vector<uint8_t> pair_blob;
   std::vector<int64_t> pair_offs{0}, pair_ptr{0};
@@ -419,6 +441,8 @@ int g2n_distances_from_path(const char* path, const g2n_options* opts, const g2n
   req.names_if_high = !req.check_ascii && o.directed;
   req.tables = out_tables;
   req.info = info;
+  req.winfo = winfo;
+  req.bad_weight = bad_weight;
   req.oriented = oriented;
   req.missing_step = missing_step;
   *oriented = 0;
@@ -427,31 +451,59 @@ int g2n_distances_from_path(const char* path, const g2n_options* opts, const g2n
     explicit Scope(const g2n::DistRequest* r) { g2n::set_dist_request(r); }
     ~Scope() { g2n::set_dist_request(nullptr); }
   } scope(&req);
+  LastBuildScope last(winfo != nullptr);
   return build_from_path(path, &o, res);
 }
 
-int g2n_seq_distance_from_path(const char* path, const g2n_options* opts, const uint8_t* seq_a, uint64_t len_a,
-                               const uint8_t* seq_b, uint64_t len_b, uint32_t* out_dist, g2n_seq_hits** hits,
-                               g2n_seq_info* info, int32_t* oriented, g2n_result** res) {
-  if (!res || !path || !out_dist || !hits || !info || !oriented) return G2N_E_ARG;
+int g2n_distances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
+                            int64_t target, int32_t mode, void* out_tables, g2n_dist_info* info, int32_t* oriented,
+                            int64_t* missing_step, g2n_result** res) {
+  if (!info || (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN)) return G2N_E_ARG;
+  return distances_from_path(path, opts, paths, source, target, mode, out_tables, info, nullptr, oriented, missing_step,
+                             nullptr, res);
+}
+
+int g2n_wdistances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
+                             int64_t target, int32_t mode, void* out_tables, g2n_wdist_info* info, int32_t* oriented,
+                             int64_t* missing_step, int32_t* bad_weight, g2n_result** res) {
+  if (!info) return G2N_E_ARG;
+  return distances_from_path(path, opts, paths, source, target, mode, out_tables, nullptr, info, oriented, missing_step,
+                             bad_weight, res);
+}
+
+int g2n_graph_weights_from_path(const char* path, const g2n_options* opts, g2n_result** res) {
+  if (!res || !path) return G2N_E_ARG;
+  *res = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  g2n_options o;
+  if (!dist_build_opts(opts, true, &o)) return G2N_E_ARG;
+  o.want_node_names = opts->want_node_names != 0;
+  LastBuildScope last(true);
+  return build_from_path(path, &o, res);
+}
+
+// g2n_seq_distance_from_path (out_dist) / g2n_seq_wdistance_from_path (out_wdist, bad_weight)
+static int seq_distance_from_path(const char* path, const g2n_options* opts, const uint8_t* seq_a, uint64_t len_a,
+                                  const uint8_t* seq_b, uint64_t len_b, uint32_t* out_dist, double* out_wdist,
+                                  g2n_seq_hits** hits, g2n_seq_info* info, int32_t* oriented, int32_t* bad_weight,
+                                  g2n_result** res) {
+  if (!res || !path || (!out_dist && !out_wdist) || !hits || !info || !oriented || (out_wdist && !bad_weight))
+    return G2N_E_ARG;
   if ((len_a && !seq_a) || (len_b && !seq_b)) return G2N_E_ARG;
   *res = nullptr;
   *hits = nullptr;
   int rc = check_opts(opts);
   if (rc) return rc;
   std::memset(info, 0, sizeof(*info));
-  *out_dist = 0xFFFFFFFFu;
+  if (out_dist) *out_dist = 0xFFFFFFFFu;
+  if (out_wdist) {
+    *out_wdist = HUGE_VAL;
+    *bad_weight = 0;
+  }
   *oriented = 0;
   g2n_options o;  // the plain graph's build, as g2n_distances_from_path's
-  g2n_options_init(&o);
-  o.directed = opts->directed != 0;
-  o.asymmetric = 1;
-  o.dtype = G2N_BOOL;
-  o.output = G2N_OUT_CSR;
-  o.want_node_names = 1;
-  o.device = opts->device;
-  o.unknown_warned = opts->unknown_warned;
-  o.test_flags = opts->test_flags;
+  if (!dist_build_opts(opts, out_wdist != nullptr, &o)) return G2N_E_ARG;
   std::unique_ptr<g2n_seq_hits> h;
   rc = g2n::guarded([&]() -> int {
     h.reset(new g2n_seq_hits());
@@ -466,6 +518,8 @@ int g2n_seq_distance_from_path(const char* path, const g2n_options* opts, const 
   req.check_ascii = opts->want_node_names != 0;
   req.names_if_high = !req.check_ascii && o.directed;
   req.dist = out_dist;
+  req.wdist = out_wdist;
+  req.bad_weight = bad_weight;
   req.hits = h.get();
   req.info = info;
   req.oriented = oriented;
@@ -473,9 +527,26 @@ int g2n_seq_distance_from_path(const char* path, const g2n_options* opts, const 
     explicit Scope(const g2n::SeqRequest* r) { g2n::set_seq_request(r); }
     ~Scope() { g2n::set_seq_request(nullptr); }
   } scope(&req);
+  LastBuildScope last(out_wdist != nullptr);
   rc = build_from_path(path, &o, res);
   *hits = h.release();
   return rc;
+}
+
+int g2n_seq_distance_from_path(const char* path, const g2n_options* opts, const uint8_t* seq_a, uint64_t len_a,
+                               const uint8_t* seq_b, uint64_t len_b, uint32_t* out_dist, g2n_seq_hits** hits,
+                               g2n_seq_info* info, int32_t* oriented, g2n_result** res) {
+  if (!out_dist) return G2N_E_ARG;
+  return seq_distance_from_path(path, opts, seq_a, len_a, seq_b, len_b, out_dist, nullptr, hits, info, oriented,
+                                nullptr, res);
+}
+
+int g2n_seq_wdistance_from_path(const char* path, const g2n_options* opts, const uint8_t* seq_a, uint64_t len_a,
+                                const uint8_t* seq_b, uint64_t len_b, double* out_dist, g2n_seq_hits** hits,
+                                g2n_seq_info* info, int32_t* oriented, int32_t* bad_weight, g2n_result** res) {
+  if (!out_dist) return G2N_E_ARG;
+  return seq_distance_from_path(path, opts, seq_a, len_a, seq_b, len_b, nullptr, out_dist, hits, info, oriented,
+                                bad_weight, res);
 }
 
 void g2n_seq_hits_get(const g2n_seq_hits* h, const int64_t** ids_a, uint64_t* n_a, const int64_t** ids_b,

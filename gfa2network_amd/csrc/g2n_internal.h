@@ -126,8 +126,17 @@ struct DistRequest {
   g2n_dist_info* info;
   int32_t* oriented;          // out: 1 when a node key ends in ":+" or ":-"
   int64_t* missing_step;      // out: -1, or a source step that is no node (nothing was searched then)
+  // g2n_wdistances_from_path: the build is a LAST build (set_last_build) and g2n_csr_path_distances_weighted
+  // searches its values; mode may be G2N_DIST_MEAN_FOLD.  winfo replaces info (null then).
+  g2n_wdist_info* winfo;      // non-null: the weighted request
+  int32_t* bad_weight;        // out: 1 when a stored value is negative or not finite (nothing was searched then)
 };
 void set_dist_request(const DistRequest* req);  // nullptr: none (thread-local)
+
+// A LAST build: while set on the calling thread, a host build produces the weighted CSR of the graph
+// parse_gfa(build_graph=True, weight_tag=T) builds (g2n_pipeline.hip csr_last) — a cell's value is that of
+// its last record carrying a numeric tag T, 1.0 without one — instead of the summed matrix.
+void set_last_build(bool on);
 
 // g2n_seq_distance_from_path: the same, for the distance between two sequences.  The staged input
 // stays on the device next to the CSR and the names; the nodes whose sequence equals a query are
@@ -139,6 +148,9 @@ struct SeqRequest {
   bool check_ascii;       // as StatsRequest::check_ascii
   bool names_if_high;     // as DistRequest::names_if_high
   uint32_t* dist;         // out: the fewest hops from a node of A to a node of B; 0xFFFFFFFF: none reached, or a set is empty
+  double* wdist;          // non-null (g2n_seq_wdistance_from_path, a LAST build; dist is null then): the shortest
+                          // weighted distance instead, +inf: none reached, or a set is empty
+  int32_t* bad_weight;    // ... and 1 when a stored value is negative or not finite (nothing was searched then)
   g2n_seq_hits* hits;     // out: the two lists of node ids, ascending
   g2n_seq_info* info;
   int32_t* oriented;      // out: 1 when a node key ends in ":+" or ":-"

@@ -594,8 +594,8 @@ __device__ inline bool span_eq(const Src& in, uint64_t off, uint64_t len, const 
 
 // Weight by the fast grammar.  Returns false when a matching tag needs the exact path.
 __device__ inline bool weight_fast(const Src& in, uint64_t ts, uint64_t e, bool has_tags,
-                                   const uint8_t* __restrict__ wt, uint32_t wtl, double* w) {
-  *w = 1.0;
+                                   const uint8_t* __restrict__ wt, uint32_t wtl, double none, double* w) {
+  *w = none;  // (no numeric tag: 1.0, or a LAST build's mark)
   if (!has_tags) return true;
   int kind = 0;  // 0 none, 1 number, 2 other
   double num = 1.0;
@@ -628,7 +628,7 @@ __device__ inline bool weight_fast(const Src& in, uint64_t ts, uint64_t e, bool 
     if (fe >= e) break;
     p = fe + 1;
   }
-  *w = kind == 1 ? num : 1.0;
+  *w = kind == 1 ? num : none;
   return true;
 }
 
@@ -764,7 +764,7 @@ __device__ inline void parse_edge(const Src& in, uint64_t i, uint64_t s, uint64_
   }
   double w = 1.0;
   if (op.has_wt) {
-    if (!weight_fast(in, L.tag_start, e, L.has_tags, op.wt, op.wt_len, &w)) {
+    if (!weight_fast(in, L.tag_start, e, L.has_tags, op.wt, op.wt_len, w_default(op.w_last), &w)) {
       unsigned long long slot = atomicAdd(&ctl->wl_count, 1ull);
       worklist[2 * slot] = i;
       worklist[2 * slot + 1] = eb;
@@ -1158,7 +1158,7 @@ __device__ inline bool lean_line(const uint8_t* buf, const uint16_t* tabm, uint3
   const uint64_t o = e * op.ktrip;
   if constexpr (kExt) {
     if (op.has_wt) {  // builders.py:205-209: the tag's value, or 1.0 without it
-      double wv = 1.0;
+      double wv = w_default(op.w_last);
       if (p[5] < n) {  // a field after the overlap: exactly one, the weight tag
         if (m || !lean_int_tag(buf, so + p[5] + 1, n - p[5] - 1, op.wt_len, op.wt_pack, &wv)) {
           is.fail = 1;
@@ -1534,7 +1534,7 @@ __global__ void __launch_bounds__(64) k_weights_slow(const uint8_t* __restrict__
       p = fe + 1;
     }
   }
-  double w = 1.0;
+  double w = w_default(op.w_last);
   if (kind == 1) {
     py_int_literal(in.ptr(best_s), best_e - best_s, true, &dec);
     if (!py_int_to_f64(&dec, &w, tmp)) {  // builders.py:209 float(val): OverflowError
@@ -1827,6 +1827,7 @@ struct HashLeanArgs {
   uint32_t wt_len;
   uint64_t wt_pack;
   double* ew;
+  uint32_t w_last;  // as ParseOpts::w_last
 };
 
 // The lean hash / direct passes' tiles, from K1's counts: lists[0] / lists[1] = how many tiles hold
@@ -1999,7 +2000,7 @@ __device__ inline bool lean_edge_names(const uint8_t* buf, const uint16_t* tabm,
   lb = p[3] - p[2] - 1;
   if constexpr (kExt) {
     *ori = (c2 == '-' ? 1u : 0u) | (c4 == '-' ? 2u : 0u);
-    *wv = 1.0;
+    *wv = w_default(H->w_last);
     if (H->has_wt && p[5] < n &&
         (m || !lean_int_tag(buf, so + p[5] + 1, n - p[5] - 1, H->wt_len, H->wt_pack, wv)))
       return false;
@@ -3604,6 +3605,151 @@ __global__ void __launch_bounds__(kTPB) k_row_sum(const uint32_t* __restrict__ s
     }
   }
   if (!sorted) ctl->unsorted[which] = 1;
+  if (staged) {
+    __syncthreads();
+    block_store(ocol, s_col, b0, nseg);
+    block_store(oval, s_val, b0, nseg);
+  }
+}
+
+// ---- LAST: the graph's weighted CSR (builders.py:246-256: G.add_edge overwrites, and sets a weight
+// only for a record that carries a numeric tag).  A cell's value is that of its last triplet in stream
+// order whose record had one — kWNone marks the others —, or 1.0 when none had.  The skeleton is
+// row_sum_one's weighted leg; the run combiner picks instead of adding, so nothing depends on an
+// addition order: no flag, no emulation.  "Last" needs the column sort to be stable: (column, stream
+// position) keys in the register network, the stable merge (ties from the left run) beyond it.
+__device__ inline double last_pick(double acc, double y) { return w_none(y) ? acc : y; }
+__device__ inline double last_value(double acc) { return w_none(acc) ? 1.0 : acc; }
+
+template <class At, class Put>
+__device__ inline uint32_t row_last_one(uint32_t len, At at, Put put, void* scr_a, void* scr_b, uint64_t s) {
+  uint32_t u = 0;
+  if (len <= kRegRow) {
+    uint64_t k[kRegRow];
+    double v[kRegRow];
+#pragma unroll
+    for (uint32_t q = 0; q < kRegRow; q++) {
+      if (q < len) {
+        const PV<double> x = at(q);
+        k[q] = ((uint64_t)x.c << 32) | q;
+        v[q] = x.v;
+      } else {
+        k[q] = ~0ull;
+        v[q] = 0.0;
+      }
+    }
+    bool sorted = true;
+#pragma unroll
+    for (uint32_t q = 1; q < kRegRow; q++)
+      if (q < len && (k[q] >> 32) < (k[q - 1] >> 32)) sorted = false;
+    if (!sorted) {
+      if (len <= 8) net_sort_kv<8>(k, v);
+      else net_sort_kv<16>(k, v);
+    }
+    uint32_t cur = (uint32_t)(k[0] >> 32);
+    double acc = v[0];
+#pragma unroll
+    for (uint32_t q = 1; q < kRegRow; q++) {
+      if (q < len) {
+        const uint32_t c = (uint32_t)(k[q] >> 32);
+        if (c != cur) {
+          put(u++, cur, last_value(acc));
+          cur = c;
+          acc = v[q];
+        } else {
+          acc = last_pick(acc, v[q]);
+        }
+      }
+    }
+    put(u++, cur, last_value(acc));
+    return u;
+  }
+  // ---- long row: the stable bottom-up merge in the row's own slices of the scratch buffers
+  PV<double>* a = (PV<double>*)scr_a + s;
+  PV<double>* b = (PV<double>*)scr_b + s;
+  bool sorted = true;
+  uint32_t prev = 0;
+  for (uint32_t q = 0; q < len; q++) {
+    const PV<double> x = at(q);
+    if (q && x.c < prev) sorted = false;
+    prev = x.c;
+    a[q] = x;
+  }
+  if (!sorted) {
+    for (uint32_t width = 1; width < len; width <<= 1) {
+      for (uint32_t lo = 0; lo < len; lo += 2 * width) {
+        const uint32_t mid = lo + width < len ? lo + width : len;
+        const uint32_t hi = lo + 2 * width < len ? lo + 2 * width : len;
+        uint32_t x = lo, y = mid, w = lo;
+        while (x < mid && y < hi) b[w++] = (a[y].c < a[x].c) ? a[y++] : a[x++];
+        while (x < mid) b[w++] = a[x++];
+        while (y < hi) b[w++] = a[y++];
+      }
+      PV<double>* t = a;
+      a = b;
+      b = t;
+    }
+  }
+  uint32_t q = 0;
+  while (q < len) {
+    const uint32_t c = a[q].c;
+    double acc = a[q].v;
+    q++;
+    while (q < len && a[q].c == c) acc = last_pick(acc, a[q++].v);
+    put(u++, c, last_value(acc));
+  }
+  return u;
+}
+
+// The LAST finish per row after the row-bucket sort (k_row_sum's layout: one row per thread, a
+// block's 256 rows own one contiguous range, staged through LDS up to kStageSumW entries): row r's
+// cells at [start[r], start[r] + ucnt[r]) of ocol / oval.
+__global__ void __launch_bounds__(kTPB) k_row_last(const uint32_t* __restrict__ start, uint64_t n_rows,
+                                                   const PV<double>* __restrict__ pv, uint32_t* __restrict__ ocol,
+                                                   double* __restrict__ oval, void* __restrict__ scr_a,
+                                                   void* __restrict__ scr_b, uint32_t* __restrict__ ucnt) {
+  __shared__ uint32_t s_col[kStageSumW];
+  __shared__ double s_val[kStageSumW];
+  const uint64_t r0 = (uint64_t)blockIdx.x * kTPB;
+  const uint64_t r1 = r0 + kTPB < n_rows ? r0 + kTPB : n_rows;
+  const uint32_t b0 = start[r0], nseg = start[r1] - b0;
+  const bool staged = nseg <= kStageSumW;  // block-uniform
+  const uint64_t r = r0 + threadIdx.x;
+  if (r < n_rows) {
+    const uint32_t s = start[r], len = start[r + 1] - s;
+    uint32_t u = 0;
+    if (len == 1) {
+      const PV<double> x = pv[s];
+      if (staged) {
+        s_col[s - b0] = x.c;
+        s_val[s - b0] = last_value(x.v);
+      } else {
+        ocol[s] = x.c;
+        oval[s] = last_value(x.v);
+      }
+      u = 1;
+    } else if (len > 1) {
+      if (staged) {
+        const uint32_t o = s - b0;
+        u = row_last_one(
+            len, [&](uint32_t q) { return pv[s + q]; },
+            [&](uint32_t j, uint32_t c, double v) {
+              s_col[o + j] = c;
+              s_val[o + j] = v;
+            },
+            scr_a, scr_b, s);
+      } else {
+        u = row_last_one(
+            len, [&](uint32_t q) { return pv[s + q]; },
+            [&](uint32_t j, uint32_t c, double v) {
+              ocol[s + j] = c;
+              oval[s + j] = v;
+            },
+            scr_a, scr_b, s);
+      }
+    }
+    ucnt[r] = u;
+  }
   if (staged) {
     __syncthreads();
     block_store(ocol, s_col, b0, nseg);

@@ -117,6 +117,7 @@ struct g2n_context {
   bool edge_text = false;     // run_edge_list's build: decimal names are left to the text render
   bool names_dec = false;     // ... and that build's names were the decimal ids (no blob written)
   bool stats_names = false;   // g2n_stats_from_path's build: names only for the ASCII check, which decimal ids pass
+  bool last_build = false;    // a LAST build (set_last_build): the graph's weighted CSR, csr_last
   uint64_t last_n_segs = 0;   // S lines of the last build (paths = records - edges - S lines)
   hipStream_t stream = nullptr;
   hipStream_t side = nullptr;   // work that overlaps the main stream (the decimal names blob)
@@ -906,6 +907,60 @@ static bool csr_partition_w(g2n_context* c, const int32_t* rows, const int32_t* 
   return true;
 }
 
+// LAST: the weighted CSR of the graph parse_gfa(build_graph=True, weight_tag=T) builds, from the
+// stream-order triplets of an asymmetric float64 build whose untagged records carry kWNone
+// (ParseOpts::w_last).  row_sums' weighted leg up to the rows' bounds — k_pack, the stable radix sort
+// by row —, then k_row_last per row and SUM's compaction.  Nothing here depends on scipy's order.
+static void csr_last(g2n_context* c, const int32_t* rows, const int32_t* cols, const double* data, uint64_t n,
+                     uint64_t n_rows, g2n_result* R) {
+  if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "more than 2^31-1 weighted matrix entries");
+  auto* key_in = dget<uint32_t>(c, S_KEYS0, n);
+  auto* key_out = dget<uint32_t>(c, S_KEYS1, n);
+  auto* start = dget<uint32_t>(c, S_RSTART0, n_rows + 1);
+  auto* ucnt = dget<uint32_t>(c, S_UCNT0, n_rows);
+  auto* ocol = dget<uint32_t>(c, S_ROUT0, n);
+  auto* oval = dget<double>(c, S_RVAL0, n);
+  PV<double>* pv_out = nullptr;
+  void *scr_a = nullptr, *scr_b = nullptr;
+  if (n) {
+    auto* pv_in = dget<PV<double>>(c, S_VALS0, n);
+    pv_out = dget<PV<double>>(c, S_VALS1, n);
+    hipLaunchKernelGGL((k_pack<double, false>), dim3(grid_for(n)), dim3(kTPB), 0, c->stream, rows, cols, data, n, 0,
+                       (int64_t)0, key_in, pv_in, (uint32_t*)nullptr);
+    sort_pairs_u32<PV<double>>(c, key_in, key_out, pv_in, pv_out, n, bits_for(n_rows));
+    scr_a = pv_in;  // the long rows' merge scratch: buffers the sort no longer needs
+    scr_b = dget<PV<double>>(c, S_RSCR, n);
+  }
+  G2N_HIP(hipMemsetAsync(&c->ctl->row_gap, 0, sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_row_bounds, dim3(grid_for(n + 1)), dim3(kTPB), 0, c->stream, key_out, n, n_rows, start, c->ctl);
+  hipLaunchKernelGGL(k_row_start, dim3(grid_for(n_rows + 1)), dim3(kTPB), 0, c->stream, key_out, n, n_rows, start,
+                     (const Ctl*)c->ctl);
+  if (n_rows)
+    hipLaunchKernelGGL(k_row_last, dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, (const uint32_t*)start, n_rows,
+                       (const PV<double>*)pv_out, ocol, oval, scr_a, scr_b, ucnt);
+  phase(c, "last");
+  auto* indptr = dget<int32_t>(c, S_INDPTR, n_rows + 1);
+  if (n_rows == 0) G2N_HIP(hipMemsetAsync(indptr, 0, sizeof(int32_t), c->stream));
+  auto* uoff = dget<uint32_t>(c, S_UOFF, n_rows);
+  excl_scan<uint32_t>(c, ucnt, uoff, n_rows);
+  auto* indices = dget<int32_t>(c, S_INDICES, n);
+  auto* odata = dget<double>(c, S_ODATA, n);
+  if (n_rows) {
+    hipLaunchKernelGGL((k_row_compact<double, false>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream,
+                       (const uint32_t*)start, (const uint32_t*)ucnt, (const uint32_t*)uoff, n_rows,
+                       (const uint32_t*)ocol, (const double*)oval, 1.0, indptr, indices, odata);
+    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, ucnt, uoff, n_rows, &c->ctl->n_keep);
+  }
+  R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
+  R->format = G2N_FMT_CSR;
+  R->indptr = indptr;
+  R->indices = indices;
+  R->data = odata;
+  R->sum_sorted = -1;  // not computed: a LAST cell does not depend on scipy's order
+  R->sum_t_sorted = -1;
+  phase(c, "csr");
+}
+
 template <class T, bool kU>
 static void assemble_t(g2n_context* c, const int32_t* rows, const int32_t* cols, const T* data, uint64_t n_trip,
                        uint64_t n_rows, uint64_t n_cols, bool maxsym, g2n_result* R, int force_unsorted = -1) {
@@ -1395,6 +1450,7 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
     lo.has_wt = xo->has_wt;
     lo.wt_len = xo->wt_len;
     lo.wt_pack = xo->wt_pack;
+    lo.w_last = xo->w_last;
     if (xo->has_wt && grouped) {
       lo.wenc = dget<uint32_t>(c, S_WENCP, slots);
       lo.wf32 = xo->wf32;
@@ -1489,6 +1545,7 @@ static void lean_ext_args(HashLeanArgs& H, const HashLeanArgs& X) {
   H.wt_len = X.wt_len;
   H.wt_pack = X.wt_pack;
   H.ew = X.ew;
+  H.w_last = X.w_last;
 }
 
 // the lean hash / direct passes' tiles (k_tile_lists): claim = tiles with S or P / O lines, edge = with edge lines
@@ -1680,7 +1737,13 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   // coordinates only — its route or slice CSR needs no stream order)
   const bool slots_out = shard_dec && (o->range_flags & G2N_RANGE_SLOTS) && !(o->weight_tag && *o->weight_tag) && !bidir &&
                          (o->range_flags & G2N_RANGE_NO_VALUES);
-  const bool grouped = (!coo_wanted || slots_out) && !c->no_group &&
+  // a LAST build (the graph's weighted CSR): per-edge weights in stream order, records without a numeric
+  // tag marked (kWNone) — never group slots, never codes
+  const bool last = c->last_build;
+  if (last && !(o->weight_tag && *o->weight_tag && dt == G2N_FLOAT64 && o->output == G2N_OUT_CSR && o->asymmetric &&
+                !bidir && !shard_dec))
+    throw Failure(G2N_E_ARG, "the graph's weighted CSR: a plain float64 CSR build with a weight tag");
+  const bool grouped = (!coo_wanted || slots_out) && !c->no_group && !last &&
                        !(c->test_flags & (kTestNoBuckets | kTestNoGroup));
   // bidirected keys / one integer weight tag: the extended tile-local instance (whole files only)
   const size_t wt_bytes = o->weight_tag ? std::strlen(o->weight_tag) : 0;
@@ -1689,6 +1752,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   xo.keep = keep;
   xo.has_wt = wt_bytes > 0;
   xo.wt_len = (uint32_t)wt_bytes;
+  xo.w_last = last ? 1u : 0u;
   for (size_t k = 0; k < wt_bytes && k < 8; k++) xo.wt_pack |= (uint64_t)(uint8_t)o->weight_tag[k] << (8 * k);
   const bool ext = bidir || wt_bytes > 0;
   // a weighted SUM CSR in dtypes whose cast of a canonical <= 9-digit integer can neither fail nor lose
@@ -1763,6 +1827,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   const size_t wtl = o->weight_tag ? std::strlen(o->weight_tag) : 0;
   op.has_wt = wtl > 0;
   op.wt_len = (uint32_t)wtl;
+  op.w_last = xo.w_last;
   if (wtl && !local_done) {  // (the full parse's copy; a tile-local build compared the tag in place: a pageable
     auto* wt = dget<uint8_t>(c, S_WT, wtl);  // H2D copy is a host wait)
     G2N_HIP(hipMemcpyAsync(wt, o->weight_tag, wtl, hipMemcpyHostToDevice, c->stream));
@@ -1828,6 +1893,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   X.wt_len = (uint32_t)wtl;
   X.wt_pack = xo.wt_pack;
   X.ew = E.w;
+  X.w_last = xo.w_last;
   // decimal names out of S order (or behind one prefix): the direct-address tier first
   NamePattern np;
   const bool direct_done = lean_hash_ok && !(c->test_flags & (kTestDictHash | kTestNoDirect)) &&
@@ -2012,7 +2078,8 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
     if (n_e && (coo_out || !uni) && !no_values && !codes_done) {
       // a weighted SUM CSR: the exact-int32 codes the bucket partition sums (csr_partition_w) beside
       uint32_t* enc = nullptr;
-      if (!uni && !maxsym && o->output == G2N_OUT_CSR && !(c->test_flags & kTestNoBuckets) && n_trip <= 0x7FFFFFFFull)
+      if (!uni && !maxsym && !last && o->output == G2N_OUT_CSR && !(c->test_flags & kTestNoBuckets) &&
+          n_trip <= 0x7FFFFFFFull)
         c->wenc = enc = dget<uint32_t>(c, S_WENC, n_trip);
 #define G2N_VALUES(T) \
   hipLaunchKernelGGL(k_values<T>, dim3(grid_for(n_e)), dim3(kTPB), 0, c->stream, E.w, n_e, ktrip, (int)uni, (T*)data, \
@@ -2063,6 +2130,11 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
       R->cols = c->gcoo.cols;
       c->gcoo.active = false;
     }
+    finish_timings(c, R);
+    return G2N_OK;
+  }
+  if (last) {  // (float64, asymmetric, never grouped: checked above)
+    csr_last(c, rows, cols, (const double*)data, n_trip, n_nodes, R);
     finish_timings(c, R);
     return G2N_OK;
   }
@@ -2358,9 +2430,10 @@ static void host_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
 static int run_host_pipeline(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, g2n_result* R) {
   struct Flag {
     g2n_context* c;
-    ~Flag() { c->stats_names = false; }
+    ~Flag() { c->stats_names = c->last_build = false; }
   } flag{c};
   c->stats_names = t_stats_request != nullptr;
+  c->last_build = t_last_build;
   return run_pipeline(c, in, len, o, R);
 }
 
@@ -3285,7 +3358,7 @@ int g2n_csr_path_distances_weighted(g2n_context* ctx, const void* d_indptr, cons
                                     g2n_wdist_info* info) {
   if (!info) return G2N_E_ARG;
   G2N_CTX_CALL(ctx, {
-    g2n::check_tables("g2n_csr_path_distances_weighted", K, mode == G2N_DIST_MEAN ? 16 : 8);
+    g2n::check_tables("g2n_csr_path_distances_weighted", K, mode != G2N_DIST_MIN ? 16 : 8);
     g2n::wpath_distances(ctx, d_indptr, d_indices, index_width, d_values, n, nnz, d_path_ptr, d_path_nodes, K, mode,
                          d_out_tables, info);
   });

@@ -42,8 +42,9 @@ static void check_csr(const std::string& who, int32_t index_width, uint64_t n, u
   if (need_rows && n == 0 && nnz) throw Failure(G2N_E_ARG, who + ": entries without rows");
 }
 
-static void check_mode(const std::string& who, int32_t mode) {
-  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN) throw Failure(G2N_E_ARG, who + ": unknown mode");
+static void check_mode(const std::string& who, int32_t mode, bool weighted = false) {
+  if (mode != G2N_DIST_MIN && mode != G2N_DIST_MEAN && !(weighted && mode == G2N_DIST_MEAN_FOLD))
+    throw Failure(G2N_E_ARG, who + ": unknown mode");
 }
 
 // the number of steps, from path_ptr's two ends (path_ptr[0] == 0; what lies between is the device's to check)
@@ -366,8 +367,9 @@ static void path_distances(g2n_context* c, const void* indptr, const void* indic
 template <class I>
 static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
                               uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
-                              uint64_t steps, bool mean, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
+                              uint64_t steps, int32_t mode, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
   const std::string who = "g2n_csr_path_distances_weighted";
+  const bool mean = mode != G2N_DIST_MIN, fold = mode == G2N_DIST_MEAN_FOLD;
   auto* st = dget<DistState>(c, S_DSTATE, 1);
   G2N_HIP(hipEventRecord(ev[0], c->stream));
   const unsigned gcap = (unsigned)c->n_cu * 8;
@@ -403,7 +405,10 @@ static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices,
   const unsigned gn = std::min(grid_for(n), gcap);
   int64_t launches = 0, rounds = 0, batches = 0;
   double ms_search = 0.0, ms_tables = 0.0;
-  for (uint64_t base = 0; base < K; base += B, batches++) {
+  const uint64_t n_batches = (K + B - 1) / B;
+  for (uint64_t k = 0; k < n_batches; k++, batches++) {
+    // (mean-fold: from the last batch to the first — a row's seeds are the rows below it, k_wdist_mean_fold)
+    const uint64_t base = (fold ? n_batches - 1 - k : k) * B;
     const uint64_t nb = std::min<uint64_t>(B, K - base);
     const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[base + nb];
     if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
@@ -438,11 +443,17 @@ static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices,
     rounds = std::max<int64_t>(rounds, last);
     // ---- the batch's rows of the tables
     G2N_HIP(hipEventRecord(ev[1], c->stream));
-    if (mean)
+    if (mean) {
       hipLaunchKernelGGL(k_wdist_mean, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes, steps, n,
                          K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base, (double*)tables,
                          D + K * K);
-    else if (steps)
+      if (fold) {
+        hipLaunchKernelGGL(k_wdist_mean_fold, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes,
+                           steps, n, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base,
+                           (double*)tables);
+        launches++;
+      }
+    } else if (steps)
       hipLaunchKernelGGL(k_wdist_min, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
                          (const uint32_t*)step_path, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb,
                          (uint32_t)base, D);
@@ -468,15 +479,14 @@ static void wpath_distances(g2n_context* c, const void* indptr, const void* indi
   const std::string who = "g2n_csr_path_distances_weighted";
   std::memset(info, 0, sizeof(*info));
   info->batch_paths = (int64_t)std::max<uint64_t>(1, std::min<uint64_t>(64, K));
-  check_mode(who, mode);
+  check_mode(who, mode, true);
   check_csr(who, index_width, n, nnz, !K || (path_ptr && tables && (!n || indptr)), !K || (indices && values), K != 0);
   if (K == 0) return;
   const uint64_t steps = path_steps_dev(c, who, path_ptr, K, path_nodes);
   Events<3> ev;
   ev.create();
   with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
-    wpath_distances_t(c, ip, ix, values, n, nnz, path_ptr, path_nodes, K, steps, mode == G2N_DIST_MEAN, tables, info,
-                      ev.e);
+    wpath_distances_t(c, ip, ix, values, n, nnz, path_ptr, path_nodes, K, steps, mode, tables, info, ev.e);
   });
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
@@ -489,11 +499,11 @@ static int distances_host(const std::string& who, const void* indptr, const void
                           const double* values, bool weighted, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
                           const int64_t* path_nodes, uint64_t K, int32_t mode, void* out_tables, int32_t device,
                           Search&& search) {
-  check_mode(who, mode);
+  check_mode(who, mode, weighted);
   check_csr(who, index_width, n, nnz, indptr && path_ptr && (!K || out_tables), indices && (!weighted || values), false);
   if (path_ptr[K] && !path_nodes) throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
   const uint64_t steps = path_steps(who, path_ptr[0], path_ptr[K]);
-  const uint64_t cell = mode == G2N_DIST_MEAN ? 16 : weighted ? 8 : 4;
+  const uint64_t cell = mode != G2N_DIST_MIN ? 16 : weighted ? 8 : 4;
   return host_call(device, [&](g2n_context* c) {
     check_tables(who, K, cell);
     const StagedCsr d = stage_csr(c, indptr, indices, values, index_width, n, nnz);
@@ -537,6 +547,20 @@ static thread_local const DistRequest* t_dist_request = nullptr;
 void set_dist_request(const DistRequest* req) { t_dist_request = req; }
 static thread_local const SeqRequest* t_seq_request = nullptr;
 void set_seq_request(const SeqRequest* req) { t_seq_request = req; }
+static thread_local bool t_last_build = false;
+void set_last_build(bool on) { t_last_build = on; }
+
+// A LAST build's stored values before a search: true when one is negative or not finite (the from-file
+// weighted calls report it instead of searching: NetworkX's result then depends on its heap's order)
+static bool bad_weights(g2n_context* c, const g2n_result& D) {
+  if (D.dtype != G2N_FLOAT64) throw Failure(G2N_E_ARG, "weighted distances: the build returned no float64 values");
+  if (!D.nnz) return false;
+  auto* st = dget<DistState>(c, S_DSTATE, 1);
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+  hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for((uint64_t)D.nnz), (unsigned)c->n_cu * 8)), dim3(256), 0,
+                     c->stream, (const double*)D.data, (uint64_t)D.nnz, st);
+  return read_dev(c, st).bad != 0;
+}
 
 // H's result as D's scalars, no matrix and no names (a stats or distance request's build)
 static void scalars_result(g2n_context* c, const g2n_result& D, HostResult* H) {
@@ -648,10 +672,19 @@ static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
   const std::string who = "g2n_distances_from_path";
   *q.oriented = 0;
   *q.missing_step = -1;
+  const bool weighted = q.winfo != nullptr;
+  if (weighted) {
+    *q.bad_weight = 0;
+    std::memset(q.winfo, 0, sizeof(*q.winfo));
+  }
   if (!names_on_device(c, D, H, who, q.check_ascii, q.names_if_high)) return;
   const uint64_t n = (uint64_t)D.n_nodes;
   if (q.n_steps >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more steps");
-  const uint64_t cell = q.mode == G2N_DIST_MEAN ? 16 : 4;
+  if (weighted && bad_weights(c, D)) {  // the graph is refused as a whole, before any step is looked up
+    *q.bad_weight = 1;
+    return;
+  }
+  const uint64_t cell = q.mode != G2N_DIST_MIN ? 16 : weighted ? 8 : 4;
   check_tables(who, q.K, cell);
   Events<2> ev;
   ev.create();
@@ -684,14 +717,21 @@ static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
   G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
   if (h[1] != ~0ull) {
     *q.missing_step = (int64_t)h[1];
-    std::memset(q.info, 0, sizeof(*q.info));
-    q.info->ms_resolve = ms;
+    if (!weighted) {
+      std::memset(q.info, 0, sizeof(*q.info));
+      q.info->ms_resolve = ms;
+    }
     return;
   }
   const uint64_t tbytes = table_bytes(q.K, cell);
   void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
-  path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, q.K, q.mode, dtab, q.info);
-  q.info->ms_resolve = ms;
+  if (weighted) {
+    wpath_distances(c, D.indptr, D.indices, D.index_width, (const double*)D.data, n, (uint64_t)D.nnz, dpp, dpn, q.K,
+                    q.mode, dtab, q.winfo);
+  } else {
+    path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, q.K, q.mode, dtab, q.info);
+    q.info->ms_resolve = ms;
+  }
   if (tbytes) G2N_HIP(hipMemcpyAsync(q.tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
@@ -703,10 +743,19 @@ static void seq_result(g2n_context* c, const g2n_result& D, HostResult* H, const
                        uint64_t len) {
   const std::string who = "g2n_seq_distance_from_path";
   *q.oriented = 0;
-  *q.dist = kDistUnreached;
+  if (q.wdist) {
+    *q.wdist = __builtin_inf();
+    *q.bad_weight = 0;
+  } else {
+    *q.dist = kDistUnreached;
+  }
   std::memset(q.info, 0, sizeof(*q.info));
   *q.hits = g2n_seq_hits();
   if (!names_on_device(c, D, H, who, q.check_ascii, q.names_if_high)) return;
+  if (q.wdist && bad_weights(c, D)) {  // the graph is refused as a whole, before any sequence is matched
+    *q.bad_weight = 1;
+    return;
+  }
   const uint64_t n = (uint64_t)D.n_nodes;
   const uint64_t n_s = c->last_n_segs;
   if (n_s >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more S lines");
@@ -828,8 +877,23 @@ static void seq_result(g2n_context* c, const g2n_result& D, HostResult* H, const
   // ---- the search: K = 2, cell [0][1]
   const int64_t pp[3] = {0, (int64_t)got[0].size(), (int64_t)pn.size()};
   auto* dpp = dget<int64_t>(c, S_DPP, 3);
-  auto* dtab = dget<uint32_t>(c, S_DTAB, 4);
   G2N_HIP(hipMemcpyAsync(dpp, pp, sizeof(pp), hipMemcpyHostToDevice, c->stream));
+  if (q.wdist) {  // the same over the LAST build's values: cell [0][1] as a double
+    auto* wtab = dget<double>(c, S_DTAB, 4);
+    g2n_wdist_info wi;
+    wpath_distances(c, D.indptr, D.indices, D.index_width, (const double*)D.data, n, (uint64_t)D.nnz, dpp, dpn, 2,
+                    G2N_DIST_MIN, wtab, &wi);
+    double tab[4];
+    G2N_HIP(hipMemcpyAsync(tab, wtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+    *q.wdist = tab[1];
+    q.info->levels = wi.rounds;
+    q.info->launches = wi.launches;
+    q.info->batches = wi.batches;
+    q.info->ms_bfs = wi.ms_search + wi.ms_tables;
+    return;
+  }
+  auto* dtab = dget<uint32_t>(c, S_DTAB, 4);
   g2n_dist_info di;
   path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, 2, G2N_DIST_MIN, dtab, &di);
   uint32_t tab[4];

@@ -246,4 +246,32 @@ __global__ void __launch_bounds__(256) k_wdist_mean(const int64_t* __restrict__ 
   C[(uint64_t)(base + b) * K + j] = cnt;
 }
 
+// mean-fold (G2N_DIST_MEAN_FOLD), after the batch's k_wdist_mean: cell (i = base + b, j > i) by one
+// thread again, the same walk over path j's steps — but from the seed S[j][i], the total over path
+// i's steps of d_j, which row j's own k_wdist_mean wrote (path j is in this batch, or in a later one:
+// the batches run from the last to the first).  The seeds are cells below the diagonal, the results
+// cells above it: no cell this kernel reads is one it writes.  C is not touched.
+__global__ void __launch_bounds__(256) k_wdist_mean_fold(const int64_t* __restrict__ path_ptr,
+                                                         const int64_t* __restrict__ path_nodes, uint64_t steps,
+                                                         uint64_t n, uint64_t K,
+                                                         const unsigned long long* __restrict__ dist, uint32_t B,
+                                                         uint32_t nb, uint32_t base, double* S) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= K * nb) return;
+  const uint32_t b = (uint32_t)(t % nb);
+  const uint64_t j = t / nb, i = (uint64_t)base + b;
+  if (j <= i) return;
+  const int64_t lo = path_ptr[j], hi = path_ptr[j + 1];
+  double sum = S[j * K + i];
+  if (lo >= 0 && lo <= hi && (uint64_t)hi <= steps)
+    for (int64_t s = lo; s < hi; s++) {
+      const int64_t v = path_nodes[s];
+      if (v < 0 || (uint64_t)v >= n) continue;
+      const unsigned long long d = dist[(uint64_t)v * B + b];
+      if (d >= kWDistInf) continue;
+      sum += __longlong_as_double((long long)d);
+    }
+  S[i * K + j] = sum;
+}
+
 }  // namespace g2n

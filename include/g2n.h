@@ -583,6 +583,8 @@ int g2n_csr_path_distances_host(const void *indptr, const void *indices, int32_t
  *   G2N_DIST_MEAN  S float64, then C uint64: S[i][j] = the sum of d_i(v) over the steps v of j that
  *                  i reaches, added in step order, left to right from 0.0, each occurrence counted
  *                  (the same bits on every run); C[i][j] = how many those are
+ *   G2N_DIST_MEAN_FOLD  (declared with g2n_wdistances_from_path below) the same, S above the diagonal
+ *                  holding the reference's running total of the cell
  * info: rounds = the relaxation rounds of the longest batch (the last round that improved a
  * distance; at most n - 1), launches = kernels launched, batch_paths = B <= 64, the paths searched
  * together (B * n * 8 bytes of distances must fit the device's free memory), batches = ceil(K / B);
@@ -645,6 +647,41 @@ void g2n_seq_hits_get(const g2n_seq_hits *h, const int64_t **ids_a, uint64_t *n_
 /* the listed nodes' keys, A's then B's: key i is blob[offsets[i] .. offsets[i + 1]), n_a + n_b + 1 offsets */
 void g2n_seq_hits_names(const g2n_seq_hits *h, const uint8_t **blob, const int64_t **offsets);
 void g2n_seq_hits_free(g2n_seq_hits *h);
+
+/* ---- the weighted graph of a file (parse_gfa(build_graph=True, weight_tag=T)) and distances over it
+ * The reference's distance helpers run Dijkstra with weight="weight" over the GRAPH a weight tag
+ * builds, whose edge lengths are not the summed matrix's: builders.py:246-256 calls G.add_edge(a, b,
+ * weight=w) only for a record that carries a numeric tag T, and add_edge overwrites.  So the length
+ * of an edge (u, v) is the weight of the LAST record of that edge, in file order, that carries a
+ * numeric T (inside a record its last T field decides, and a value that is no number is none), or 1
+ * when no record does; in an undirected build (u, v) and (v, u) are one edge.
+ *
+ * g2n_graph_weights_from_path builds that matrix ("LAST"; of opts: directed, weight_tag — required —,
+ * want_node_names, device, unknown_warned, test_flags): *res holds a float64 CSR, one stored cell per
+ * distinct edge (both cells of an undirected one), columns ascending within a row, an explicit 0.0
+ * kept, nodes in first-touch order, with the names when want_node_names.  G2N_E_INT_TOO_LARGE as
+ * ever for an integer tag float() overflows on.
+ *
+ * g2n_wdistances_from_path / g2n_seq_wdistance_from_path are g2n_distances_from_path /
+ * g2n_seq_distance_from_path over that matrix with g2n_csr_path_distances_weighted as the search:
+ * out_tables as that function's (min: K x K float64; mean and mean-fold: S float64 then C uint64),
+ * *out_dist float64, +inf where the hop call has 0xFFFFFFFF.  *bad_weight = 1 when a stored value is
+ * negative, NaN or infinite: nothing is searched then (NetworkX's result on such a graph depends on
+ * its heap's order).  A value a later record replaced is not stored and does not count.
+ *
+ * G2N_DIST_MEAN_FOLD (the weighted searches only) is G2N_DIST_MEAN with, for i < j, S[i][j] = the
+ * running total genome_distance_matrix keeps for the cell (analysis.py:254-264): it starts at 0.0,
+ * adds d_j(u) over the steps u of path i that j reaches, then d_i(v) over the steps v of path j —
+ * S[j][i] continued over path j's steps, not S[i][j] + S[j][i], which differs in the last bit for
+ * general floats.  S[i][j] for i >= j and C are G2N_DIST_MEAN's. */
+#define G2N_DIST_MEAN_FOLD 2
+int g2n_graph_weights_from_path(const char *path, const g2n_options *opts, g2n_result **res);
+int g2n_wdistances_from_path(const char *path, const g2n_options *opts, const g2n_paths *paths, int64_t source,
+                             int64_t target, int32_t mode, void *out_tables, g2n_wdist_info *info, int32_t *oriented,
+                             int64_t *missing_step, int32_t *bad_weight, g2n_result **res);
+int g2n_seq_wdistance_from_path(const char *path, const g2n_options *opts, const uint8_t *seq_a, uint64_t len_a,
+                                const uint8_t *seq_b, uint64_t len_b, double *out_dist, g2n_seq_hits **hits,
+                                g2n_seq_info *info, int32_t *oriented, int32_t *bad_weight, g2n_result **res);
 
 #ifdef __cplusplus
 }
