@@ -134,7 +134,7 @@ struct DistRequest {
 void set_dist_request(const DistRequest* req);  // nullptr: none (thread-local)
 
 // A LAST build: while set on the calling thread, a host build produces the weighted CSR of the graph
-// parse_gfa(build_graph=True, weight_tag=T) builds (g2n_pipeline.hip csr_last) — a cell's value is that of
+// parse_gfa(build_graph=True, weight_tag=T) builds (g2n_pipeline.hip csr_last: the row finish's Last policy) — a cell's value is that of
 // its last record carrying a numeric tag T, 1.0 without one — instead of the summed matrix.
 void set_last_build(bool on);
 

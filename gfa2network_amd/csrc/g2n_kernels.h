@@ -127,7 +127,7 @@ struct ParseOpts {
   // beside rows / cols in the group slots instead of one double per edge line (op.ew)
   uint32_t* wenc;
   uint32_t wf32;
-  // a LAST build (the graph's weighted CSR, k_row_last): a record without a numeric weight tag carries
+  // a LAST build (the graph's weighted CSR, k_row_finish<RowLast>): a record without a numeric weight tag carries
   // kWNone instead of 1.0 (w_default); 0 in every other build
   uint32_t w_last;
 };
@@ -136,7 +136,7 @@ constexpr uint32_t kGroupShift = 5;
 // "No numeric weight tag on this record", in the per-edge weights of a LAST build: a quiet NaN with a
 // non-zero low payload.  A parsed weight is never this pattern: py_float_literal (pylit.h) yields only
 // the canonical NaNs 0x7FF8000000000000 / 0xFFF8000000000000 (float("nan") / float("-nan")), an integer
-// tag no NaN at all, and nothing between the parse and k_row_last does arithmetic on a weight (k_values'
+// tag no NaN at all, and nothing between the parse and k_row_finish<RowLast> does arithmetic on a weight (k_values'
 // cast to float64, k_tile_compact, k_pack and the radix sort copy its bits).
 constexpr unsigned long long kWNoneBits = 0x7FF8000000000001ull;
 static_assert((kWNoneBits & 0xFFF8000000000000ull) == 0x7FF8000000000000ull, "kWNone is a positive quiet NaN");

@@ -3333,7 +3333,7 @@ constexpr uint32_t kRegRow = 16;  // rows up to this many entries are sorted in 
 // sorted entries (start[r0] .. start[r0 + 256]) and of every per-row output, so the block stages
 // its ranges through LDS: coalesced loads and stores of the whole range, lane-strided accesses
 // only in LDS.  A block whose range exceeds the LDS capacity works on global memory directly.
-constexpr uint32_t kStageSumU = 4096;  // entries a k_row_sum block stages (unweighted / weighted)
+constexpr uint32_t kStageSumU = 4096;  // entries a k_row_finish block stages (Count / Sum<T> and Last)
 constexpr uint32_t kStageSumW = 2048;
 constexpr uint32_t kStageMaxU = 2048;  // entries per staged range in k_row_max / k_row_compact
 constexpr uint32_t kStageMaxW = 1024;
@@ -3364,224 +3364,222 @@ __device__ inline void block_store(E* __restrict__ g, const E* __restrict__ lds,
   for (uint32_t i = threadIdx.x; i < n; i += kTPB) g[base + i] = lds[i];
 }
 
+// ---- the row finish: one skeleton (row_finish_one, k_row_finish), three policies.  A policy names
+// the element the row-bucket sort carried (E: the bare column, or PV<T>), the value a cell stores (V),
+// how a run of equal columns folds into one cell (add, left to right in stream order, then fin), the
+// LDS capacity of a block's output, whether the kernel reports to Ctl (unsorted / flagged) and whether
+// the long-row walk gathers SUM's float-order evidence.  All of it is resolved at compile time.
+__device__ inline uint32_t el_col(uint32_t e) { return e; }
+__device__ inline uint32_t el_val(uint32_t) { return 1u; }
+template <class T>
+__device__ inline uint32_t el_col(const PV<T>& e) { return e.c; }
+template <class T>
+__device__ inline T el_val(const PV<T>& e) { return e.v; }
+
+// Count: the uniform build (every value is dtype(1), a cell stores its run length).  Equal columns
+// are indistinguishable, so its register sort keeps 32-bit keys and no payload.
+struct RowCount {
+  using E = uint32_t;
+  using V = uint32_t;
+  static constexpr uint32_t kCap = kStageSumU;
+  static constexpr bool kReports = true;
+  static constexpr bool kOrder = false;
+  __device__ static V add(V x, V y) { return x + y; }
+  __device__ static V fin(V x) { return x; }
+};
+// Sum<T>: the weighted coo.tocsr(), scipy's `x += y` in T.
+template <class T>
+struct RowSum {
+  using E = PV<T>;
+  using V = T;
+  static constexpr uint32_t kCap = kStageSumW;
+  static constexpr bool kReports = true;
+  static constexpr bool kOrder = std::is_floating_point<T>::value;  // (= Acc<T>::is_float())
+  __device__ static V add(V x, V y) { return Acc<T>::add(x, y); }
+  __device__ static V fin(V x) { return x; }
+};
+// Last: the graph's weighted CSR (builders.py:246-256: G.add_edge overwrites, and sets a weight only
+// for a record that carries a numeric tag).  A cell's value is that of its last triplet in stream
+// order whose record had one — kWNone marks the others —, or 1.0 when none had.  The combiner picks
+// instead of adding, so nothing depends on an addition order: no flag, no emulation, no report.
+struct RowLast {
+  using E = PV<double>;
+  using V = double;
+  static constexpr uint32_t kCap = kStageSumW;
+  static constexpr bool kReports = false;
+  static constexpr bool kOrder = false;
+  __device__ static V add(V acc, V y) { return w_none(y) ? acc : y; }
+  __device__ static V fin(V acc) { return w_none(acc) ? 1.0 : acc; }
+};
+template <class T, bool kUniform>
+using RowSumPolicy = typename std::conditional<kUniform, RowCount, RowSum<T>>::type;
+
+// Stable bottom-up merge sort of a[0, len) by column, ascending, with b as the other buffer; returns
+// the one that holds the result.  Ties are taken from the left run: equal columns keep their stream
+// order, which is what SUM's left-to-right run sums and LAST's "last" both mean.
+template <class E>
+__device__ inline E* row_merge_sort(E* a, E* b, uint32_t len) {
+  for (uint32_t width = 1; width < len; width <<= 1) {
+    for (uint32_t lo = 0; lo < len; lo += 2 * width) {
+      const uint32_t mid = lo + width < len ? lo + width : len;
+      const uint32_t hi = lo + 2 * width < len ? lo + 2 * width : len;
+      uint32_t x = lo, y = mid, w = lo;
+      while (x < mid && y < hi) b[w++] = (el_col(a[y]) < el_col(a[x])) ? a[y++] : a[x++];
+      while (x < mid) b[w++] = a[x++];
+      while (y < hi) b[w++] = a[y++];
+    }
+    E* t = a;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
 // One row: entries in stream order (at(q), q < len; after the stable row-bucket sort) -> sorted
-// unique (column, count | sum), put(j, column, value).  Rows <= kRegRow entries: register
-// sorting network on (column, stream position) keys, i.e. a stable sort.  Longer rows: stable
-// bottom-up merge sort in global scratch (a, b: the row's own slices of two buffers the
-// row-bucket sort left free).  flag: the row's float sums could depend on std::sort's order.
-template <class T, bool kUniform, class At, class Put>
-__device__ inline uint32_t row_sum_one(uint32_t len, At at, Put put, void* scr_a, void* scr_b, uint64_t s,
-                                       bool& sorted, bool& flag) {
-  using V = typename RowVal<T, kUniform>::type;
+// unique (column, value), put(j, column, value).  Rows <= kRegRow entries: register sorting network
+// on (column, stream position) keys, i.e. a stable sort (a payload-free element: on the column alone).
+// Longer rows: row_merge_sort in global scratch (a, b: the row's own slices of two buffers the
+// row-bucket sort left free).  flag: the row's float sums could depend on std::sort's order (only a
+// long row of a policy with kOrder can set it).
+template <class P, class At, class Put>
+__device__ inline uint32_t row_finish_one(uint32_t len, At at, Put put, void* scr_a, void* scr_b, uint64_t s,
+                                          bool& sorted, bool& flag) {
+  using E = typename P::E;
+  using V = typename P::V;
+  constexpr bool kPayload = !std::is_same<E, uint32_t>::value;
   uint32_t u = 0;
   sorted = true;
   flag = false;
   if (len <= kRegRow) {
-    if constexpr (kUniform) {
-      uint32_t k[kRegRow];
+    using K = typename std::conditional<kPayload, uint64_t, uint32_t>::type;
+    constexpr int kColShift = kPayload ? 32 : 0;
+    K k[kRegRow];
+    V v[kRegRow];
 #pragma unroll
-      for (uint32_t q = 0; q < kRegRow; q++) k[q] = q < len ? at(q) : 0xFFFFFFFFu;
+    for (uint32_t q = 0; q < kRegRow; q++) {
+      if (q < len) {
+        const E x = at(q);
+        k[q] = kPayload ? (K)(((uint64_t)el_col(x) << 32) | q) : (K)el_col(x);
+        v[q] = el_val(x);
+      } else {
+        k[q] = (K)~0ull;
+        v[q] = (V)0;
+      }
+    }
 #pragma unroll
-      for (uint32_t q = 1; q < kRegRow; q++)
-        if (q < len && k[q] < k[q - 1]) sorted = false;
-      if (!sorted) {
+    for (uint32_t q = 1; q < kRegRow; q++)
+      if (q < len && (k[q] >> kColShift) < (k[q - 1] >> kColShift)) sorted = false;
+    if (!sorted) {
+      if constexpr (kPayload) {
+        if (len <= 8) net_sort_kv<8>(k, v);
+        else net_sort_kv<16>(k, v);
+      } else {
         if (len <= 8) net_sort<8>(k);
         else net_sort<16>(k);
       }
-      uint32_t cur = k[0], cnt = 1;
-#pragma unroll
-      for (uint32_t q = 1; q < kRegRow; q++) {
-        if (q < len) {
-          if (k[q] != cur) {
-            put(u++, cur, (V)cnt);
-            cur = k[q];
-            cnt = 0;
-          }
-          cnt++;
-        }
-      }
-      put(u++, cur, (V)cnt);
-    } else {
-      uint64_t k[kRegRow];
-      T v[kRegRow];
-#pragma unroll
-      for (uint32_t q = 0; q < kRegRow; q++) {
-        if (q < len) {
-          const PV<T> x = at(q);
-          k[q] = ((uint64_t)x.c << 32) | q;
-          v[q] = x.v;
-        } else {
-          k[q] = ~0ull;
-          v[q] = (T)0;
-        }
-      }
-#pragma unroll
-      for (uint32_t q = 1; q < kRegRow; q++)
-        if (q < len && (k[q] >> 32) < (k[q - 1] >> 32)) sorted = false;
-      if (!sorted) {
-        if (len <= 8) net_sort_kv<8>(k, v);
-        else net_sort_kv<16>(k, v);
-      }
-      uint32_t cur = (uint32_t)(k[0] >> 32);
-      T acc = v[0];
-#pragma unroll
-      for (uint32_t q = 1; q < kRegRow; q++) {
-        if (q < len) {
-          const uint32_t c = (uint32_t)(k[q] >> 32);
-          if (c != cur) {
-            put(u++, cur, acc);
-            cur = c;
-            acc = v[q];
-          } else {
-            acc = Acc<T>::add(acc, v[q]);
-          }
-        }
-      }
-      put(u++, cur, acc);
     }
+    uint32_t cur = (uint32_t)(k[0] >> kColShift);
+    V acc = v[0];
+#pragma unroll
+    for (uint32_t q = 1; q < kRegRow; q++) {
+      if (q < len) {
+        const uint32_t c = (uint32_t)(k[q] >> kColShift);
+        if (c != cur) {
+          put(u++, cur, P::fin(acc));
+          cur = c;
+          acc = v[q];
+        } else {
+          acc = P::add(acc, v[q]);
+        }
+      }
+    }
+    put(u++, cur, P::fin(acc));
     return u;
   }
   // ---- long row
-  if constexpr (kUniform) {
-    uint32_t* a = (uint32_t*)scr_a + s;
-    uint32_t* b = (uint32_t*)scr_b + s;
-    uint32_t prev = 0;
-    for (uint32_t q = 0; q < len; q++) {
-      const uint32_t c = at(q);
-      if (q && c < prev) sorted = false;
-      prev = c;
-      a[q] = c;
+  E* a = (E*)scr_a + s;
+  E* b = (E*)scr_b + s;
+  uint32_t prev = 0;
+  for (uint32_t q = 0; q < len; q++) {
+    const E x = at(q);
+    if (q && el_col(x) < prev) sorted = false;
+    prev = el_col(x);
+    a[q] = x;
+  }
+  if (!sorted) a = row_merge_sort(a, b, len);
+  uint32_t q = 0;
+  while (q < len) {  // left-to-right run folds
+    const uint32_t c = el_col(a[q]), q0 = q;
+    V x = el_val(a[q]);
+    bool exact = true;
+    double sabs = 0.0;
+    uint32_t nans = 0;
+    if constexpr (P::kOrder) {
+      exact = exact_term(x);
+      sabs = __builtin_fabs((double)x);
+      nans = x != x;
     }
-    if (!sorted) {
-      for (uint32_t width = 1; width < len; width <<= 1) {
-        for (uint32_t lo = 0; lo < len; lo += 2 * width) {
-          const uint32_t mid = lo + width < len ? lo + width : len;
-          const uint32_t hi = lo + 2 * width < len ? lo + 2 * width : len;
-          uint32_t x = lo, y = mid, w = lo;
-          while (x < mid && y < hi) b[w++] = (a[y] < a[x]) ? a[y++] : a[x++];
-          while (x < mid) b[w++] = a[x++];
-          while (y < hi) b[w++] = a[y++];
-        }
-        uint32_t* t = a;
-        a = b;
-        b = t;
+    q++;
+    while (q < len && el_col(a[q]) == c) {
+      const V y = el_val(a[q]);
+      if constexpr (P::kOrder) {
+        exact = exact && exact_term(y);
+        sabs += __builtin_fabs((double)y);
+        nans += y != y;
       }
-    }
-    uint32_t q = 0;
-    while (q < len) {
-      const uint32_t c = a[q], q0 = q;
-      while (q < len && a[q] == c) q++;
-      put(u++, c, (V)(q - q0));
-    }
-  } else {
-    PV<T>* a = (PV<T>*)scr_a + s;
-    PV<T>* b = (PV<T>*)scr_b + s;
-    uint32_t prev = 0;
-    for (uint32_t q = 0; q < len; q++) {
-      const PV<T> x = at(q);
-      if (q && x.c < prev) sorted = false;
-      prev = x.c;
-      a[q] = x;
-    }
-    if (!sorted) {
-      for (uint32_t width = 1; width < len; width <<= 1) {
-        for (uint32_t lo = 0; lo < len; lo += 2 * width) {
-          const uint32_t mid = lo + width < len ? lo + width : len;
-          const uint32_t hi = lo + 2 * width < len ? lo + 2 * width : len;
-          uint32_t x = lo, y = mid, w = lo;
-          while (x < mid && y < hi) b[w++] = (a[y].c < a[x].c) ? a[y++] : a[x++];
-          while (x < mid) b[w++] = a[x++];
-          while (y < hi) b[w++] = a[y++];
-        }
-        PV<T>* t = a;
-        a = b;
-        b = t;
-      }
-    }
-    uint32_t q = 0;
-    while (q < len) {  // left-to-right run sums
-      const uint32_t c = a[q].c, q0 = q;
-      T x = a[q].v;
-      bool exact = true;
-      double sabs = 0.0;
-      uint32_t nans = 0;
-      if (Acc<T>::is_float()) {
-        exact = exact_term(x);
-        sabs = __builtin_fabs((double)x);
-        nans = x != x;
-      }
+      x = P::add(x, y);
       q++;
-      while (q < len && a[q].c == c) {
-        const T y = a[q].v;
-        if (Acc<T>::is_float()) {
-          exact = exact && exact_term(y);
-          sabs += __builtin_fabs((double)y);
-          nans += y != y;
-        }
-        x = Acc<T>::add(x, y);
-        q++;
-      }
-      // a group of >= 3 terms whose sum depends on their order (std::sort on > 16 elements is
-      // not an insertion sort, so scipy's order is not the stable one), or one that holds two NaNs:
-      // x86 keeps the first NaN operand's payload and sign, so even a pair's sum follows the order
-      if (Acc<T>::is_float() && ((q - q0 >= 3 && !(exact && sabs < Acc<T>::limit())) || nans >= 2))
-        flag = true;
-      put(u++, c, x);
     }
+    // a group of >= 3 terms whose sum depends on their order (std::sort on > 16 elements is
+    // not an insertion sort, so scipy's order is not the stable one), or one that holds two NaNs:
+    // x86 keeps the first NaN operand's payload and sign, so even a pair's sum follows the order
+    if constexpr (P::kOrder) {
+      if ((q - q0 >= 3 && !(exact && sabs < Acc<V>::limit())) || nans >= 2) flag = true;
+    }
+    put(u++, c, P::fin(x));
   }
   return u;
 }
 
-// coo.tocsr() per row after the row-bucket sort: row r's unique entries at
-// [start[r], start[r] + ucnt[r]) of ocol / oval.
-template <class T, bool kUniform>
-__global__ void __launch_bounds__(kTPB) k_row_sum(const uint32_t* __restrict__ start, uint64_t n_rows,
-                                                  const PV<T>* __restrict__ pv, const uint32_t* __restrict__ pc,
-                                                  uint32_t* __restrict__ ocol,
-                                                  typename RowVal<T, kUniform>::type* __restrict__ oval,
-                                                  void* __restrict__ scr_a, void* __restrict__ scr_b,
-                                                  uint32_t* __restrict__ ucnt, uint8_t* __restrict__ rowflag,
-                                                  Ctl* ctl, int which) {
-  using V = typename RowVal<T, kUniform>::type;
-  using In = typename std::conditional<kUniform, uint32_t, PV<T>>::type;
-  constexpr uint32_t kCap = kUniform ? kStageSumU : kStageSumW;
+// The finish per row after the row-bucket sort (coo.tocsr() for Count and Sum<T>, the graph's
+// weighted CSR for Last): row r's unique entries at [start[r], start[r] + ucnt[r]) of ocol / oval.
+// rowflag, ctl and which are read only by a policy that reports.
+template <class P>
+__global__ void __launch_bounds__(kTPB) k_row_finish(const uint32_t* __restrict__ start, uint64_t n_rows,
+                                                     const typename P::E* __restrict__ gin,
+                                                     uint32_t* __restrict__ ocol, typename P::V* __restrict__ oval,
+                                                     void* __restrict__ scr_a, void* __restrict__ scr_b,
+                                                     uint32_t* __restrict__ ucnt, uint8_t* __restrict__ rowflag,
+                                                     Ctl* ctl, int which) {
+  using E = typename P::E;
+  using V = typename P::V;
   // the row loads are independent (unrolled) and stay direct; only the lane-strided stores of
   // the unique entries are staged
-  __shared__ uint32_t s_col[kCap];
-  __shared__ V s_val[kCap];
-  const In* gin = kUniform ? (const In*)(const void*)pc : (const In*)(const void*)pv;
+  __shared__ uint32_t s_col[P::kCap];
+  __shared__ V s_val[P::kCap];
   const uint64_t r0 = (uint64_t)blockIdx.x * kTPB;
   const uint64_t r1 = r0 + kTPB < n_rows ? r0 + kTPB : n_rows;
   const uint32_t b0 = start[r0], nseg = start[r1] - b0;
-  const bool staged = nseg <= kCap;  // block-uniform
+  const bool staged = nseg <= P::kCap;  // block-uniform
   const uint64_t r = r0 + threadIdx.x;
   bool sorted = true, flag = false;
   if (r < n_rows) {
     const uint32_t s = start[r], len = start[r + 1] - s;
     uint32_t u = 0;
     if (len == 1) {
-      const In x = gin[s];
-      uint32_t c;
-      V v;
-      if constexpr (kUniform) {
-        c = x;
-        v = 1u;
-      } else {
-        c = x.c;
-        v = x.v;
-      }
+      const E x = gin[s];
       if (staged) {
-        s_col[s - b0] = c;
-        s_val[s - b0] = v;
+        s_col[s - b0] = el_col(x);
+        s_val[s - b0] = P::fin(el_val(x));
       } else {
-        ocol[s] = c;
-        oval[s] = v;
+        ocol[s] = el_col(x);
+        oval[s] = P::fin(el_val(x));
       }
       u = 1;
     } else if (len > 1) {
       if (staged) {
         const uint32_t o = s - b0;
-        u = row_sum_one<T, kUniform>(
+        u = row_finish_one<P>(
             len, [&](uint32_t q) { return gin[s + q]; },
             [&](uint32_t j, uint32_t c, V v) {
               s_col[o + j] = c;
@@ -3589,7 +3587,7 @@ __global__ void __launch_bounds__(kTPB) k_row_sum(const uint32_t* __restrict__ s
             },
             scr_a, scr_b, s, sorted, flag);
       } else {
-        u = row_sum_one<T, kUniform>(
+        u = row_finish_one<P>(
             len, [&](uint32_t q) { return gin[s + q]; },
             [&](uint32_t j, uint32_t c, V v) {
               ocol[s + j] = c;
@@ -3599,156 +3597,15 @@ __global__ void __launch_bounds__(kTPB) k_row_sum(const uint32_t* __restrict__ s
       }
     }
     ucnt[r] = u;
-    if (flag) {
-      rowflag[r] = 1;
-      ctl->flagged[which] = 1;
-    }
-  }
-  if (!sorted) ctl->unsorted[which] = 1;
-  if (staged) {
-    __syncthreads();
-    block_store(ocol, s_col, b0, nseg);
-    block_store(oval, s_val, b0, nseg);
-  }
-}
-
-// ---- LAST: the graph's weighted CSR (builders.py:246-256: G.add_edge overwrites, and sets a weight
-// only for a record that carries a numeric tag).  A cell's value is that of its last triplet in stream
-// order whose record had one — kWNone marks the others —, or 1.0 when none had.  The skeleton is
-// row_sum_one's weighted leg; the run combiner picks instead of adding, so nothing depends on an
-// addition order: no flag, no emulation.  "Last" needs the column sort to be stable: (column, stream
-// position) keys in the register network, the stable merge (ties from the left run) beyond it.
-__device__ inline double last_pick(double acc, double y) { return w_none(y) ? acc : y; }
-__device__ inline double last_value(double acc) { return w_none(acc) ? 1.0 : acc; }
-
-template <class At, class Put>
-__device__ inline uint32_t row_last_one(uint32_t len, At at, Put put, void* scr_a, void* scr_b, uint64_t s) {
-  uint32_t u = 0;
-  if (len <= kRegRow) {
-    uint64_t k[kRegRow];
-    double v[kRegRow];
-#pragma unroll
-    for (uint32_t q = 0; q < kRegRow; q++) {
-      if (q < len) {
-        const PV<double> x = at(q);
-        k[q] = ((uint64_t)x.c << 32) | q;
-        v[q] = x.v;
-      } else {
-        k[q] = ~0ull;
-        v[q] = 0.0;
+    if constexpr (P::kReports) {
+      if (flag) {
+        rowflag[r] = 1;
+        ctl->flagged[which] = 1;
       }
     }
-    bool sorted = true;
-#pragma unroll
-    for (uint32_t q = 1; q < kRegRow; q++)
-      if (q < len && (k[q] >> 32) < (k[q - 1] >> 32)) sorted = false;
-    if (!sorted) {
-      if (len <= 8) net_sort_kv<8>(k, v);
-      else net_sort_kv<16>(k, v);
-    }
-    uint32_t cur = (uint32_t)(k[0] >> 32);
-    double acc = v[0];
-#pragma unroll
-    for (uint32_t q = 1; q < kRegRow; q++) {
-      if (q < len) {
-        const uint32_t c = (uint32_t)(k[q] >> 32);
-        if (c != cur) {
-          put(u++, cur, last_value(acc));
-          cur = c;
-          acc = v[q];
-        } else {
-          acc = last_pick(acc, v[q]);
-        }
-      }
-    }
-    put(u++, cur, last_value(acc));
-    return u;
   }
-  // ---- long row: the stable bottom-up merge in the row's own slices of the scratch buffers
-  PV<double>* a = (PV<double>*)scr_a + s;
-  PV<double>* b = (PV<double>*)scr_b + s;
-  bool sorted = true;
-  uint32_t prev = 0;
-  for (uint32_t q = 0; q < len; q++) {
-    const PV<double> x = at(q);
-    if (q && x.c < prev) sorted = false;
-    prev = x.c;
-    a[q] = x;
-  }
-  if (!sorted) {
-    for (uint32_t width = 1; width < len; width <<= 1) {
-      for (uint32_t lo = 0; lo < len; lo += 2 * width) {
-        const uint32_t mid = lo + width < len ? lo + width : len;
-        const uint32_t hi = lo + 2 * width < len ? lo + 2 * width : len;
-        uint32_t x = lo, y = mid, w = lo;
-        while (x < mid && y < hi) b[w++] = (a[y].c < a[x].c) ? a[y++] : a[x++];
-        while (x < mid) b[w++] = a[x++];
-        while (y < hi) b[w++] = a[y++];
-      }
-      PV<double>* t = a;
-      a = b;
-      b = t;
-    }
-  }
-  uint32_t q = 0;
-  while (q < len) {
-    const uint32_t c = a[q].c;
-    double acc = a[q].v;
-    q++;
-    while (q < len && a[q].c == c) acc = last_pick(acc, a[q++].v);
-    put(u++, c, last_value(acc));
-  }
-  return u;
-}
-
-// The LAST finish per row after the row-bucket sort (k_row_sum's layout: one row per thread, a
-// block's 256 rows own one contiguous range, staged through LDS up to kStageSumW entries): row r's
-// cells at [start[r], start[r] + ucnt[r]) of ocol / oval.
-__global__ void __launch_bounds__(kTPB) k_row_last(const uint32_t* __restrict__ start, uint64_t n_rows,
-                                                   const PV<double>* __restrict__ pv, uint32_t* __restrict__ ocol,
-                                                   double* __restrict__ oval, void* __restrict__ scr_a,
-                                                   void* __restrict__ scr_b, uint32_t* __restrict__ ucnt) {
-  __shared__ uint32_t s_col[kStageSumW];
-  __shared__ double s_val[kStageSumW];
-  const uint64_t r0 = (uint64_t)blockIdx.x * kTPB;
-  const uint64_t r1 = r0 + kTPB < n_rows ? r0 + kTPB : n_rows;
-  const uint32_t b0 = start[r0], nseg = start[r1] - b0;
-  const bool staged = nseg <= kStageSumW;  // block-uniform
-  const uint64_t r = r0 + threadIdx.x;
-  if (r < n_rows) {
-    const uint32_t s = start[r], len = start[r + 1] - s;
-    uint32_t u = 0;
-    if (len == 1) {
-      const PV<double> x = pv[s];
-      if (staged) {
-        s_col[s - b0] = x.c;
-        s_val[s - b0] = last_value(x.v);
-      } else {
-        ocol[s] = x.c;
-        oval[s] = last_value(x.v);
-      }
-      u = 1;
-    } else if (len > 1) {
-      if (staged) {
-        const uint32_t o = s - b0;
-        u = row_last_one(
-            len, [&](uint32_t q) { return pv[s + q]; },
-            [&](uint32_t j, uint32_t c, double v) {
-              s_col[o + j] = c;
-              s_val[o + j] = v;
-            },
-            scr_a, scr_b, s);
-      } else {
-        u = row_last_one(
-            len, [&](uint32_t q) { return pv[s + q]; },
-            [&](uint32_t j, uint32_t c, double v) {
-              ocol[s + j] = c;
-              oval[s + j] = v;
-            },
-            scr_a, scr_b, s);
-      }
-    }
-    ucnt[r] = u;
+  if constexpr (P::kReports) {
+    if (!sorted) ctl->unsorted[which] = 1;
   }
   if (staged) {
     __syncthreads();
@@ -4303,8 +4160,6 @@ __global__ void __launch_bounds__(kTPB) k_edge_dec_text(const int32_t* __restric
 #define G2N_INST_U(T, U)                                                                                        \
   template __global__ void k_pack<T, U>(const int32_t*, const int32_t*, const T*, uint64_t, int, int64_t, uint32_t*, \
                                         PV<T>*, uint32_t*);                                                      \
-  template __global__ void k_row_sum<T, U>(const uint32_t*, uint64_t, const PV<T>*, const uint32_t*, uint32_t*,   \
-                                           RowVal<T, U>::type*, void*, void*, uint32_t*, uint8_t*, Ctl*, int);   \
   template __global__ void k_row_compact<T, U>(const uint32_t*, const uint32_t*, const uint32_t*, uint64_t,      \
                                                const uint32_t*, const RowVal<T, U>::type*, T, int32_t*,          \
                                                int32_t*, T*);                                                    \
@@ -4322,6 +4177,8 @@ __global__ void __launch_bounds__(kTPB) k_edge_dec_text(const int32_t* __restric
                                          const uint32_t*, int, int, int32_t*, int32_t*, T*, Ctl*);                \
   template __global__ void k_row_emulate<T>(const uint32_t*, uint64_t, const uint8_t*, const PV<T>*, uint32_t*,    \
                                             T*, KV<int32_t, T>*);                                                 \
+  template __global__ void k_row_finish<RowSum<T>>(const uint32_t*, uint64_t, const PV<T>*, uint32_t*, T*, void*,  \
+                                                    void*, uint32_t*, uint8_t*, Ctl*, int);                       \
   G2N_INST_U(T, true)                                                                                            \
   G2N_INST_U(T, false)
 G2N_INST(uint8_t)
@@ -4331,5 +4188,10 @@ G2N_INST(float)
 G2N_INST(double)
 #undef G2N_INST
 #undef G2N_INST_U
+// (the policies that do not depend on the dtype: once)
+template __global__ void k_row_finish<RowCount>(const uint32_t*, uint64_t, const uint32_t*, uint32_t*, uint32_t*, void*,
+                                                void*, uint32_t*, uint8_t*, Ctl*, int);
+template __global__ void k_row_finish<RowLast>(const uint32_t*, uint64_t, const PV<double>*, uint32_t*, double*, void*,
+                                               void*, uint32_t*, uint8_t*, Ctl*, int);
 
 }  // namespace g2n

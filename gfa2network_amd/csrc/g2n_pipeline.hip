@@ -377,71 +377,95 @@ static void sort_pairs_u32(g2n_context* c, const uint32_t* kin, uint32_t* kout, 
   }
 }
 
-// coo.tocsr() of one orientation (transposed: of A.T), up to the per-row sorted unique entries.
-// side: which set of per-row buffers (0: A, 1: A.T); transposed: key on the column;
-// base: first row of the slice; force_unsorted: -1 = this matrix decides scipy's global
-// has_sorted_indices, else the caller's verdict (sharded builds: the OR over all slices).
+// One orientation's entries sorted stably by row: row r's, in stream order, at in[start[r], start[r + 1]).
+template <class E>
+struct RowSorted {
+  uint32_t* start;
+  const E* in;          // the bare column (uniform build) or PV<T>
+  void *scr_a, *scr_b;  // long-row merge scratch: buffers the sort no longer needs
+};
+
+// The row path up to the rows' bounds: k_pack (transposed: key on the column; base: first row of the
+// slice), the stable radix sort by row, k_row_bounds / k_row_start.  side: which set of per-row
+// buffers (0: A, 1: A.T).
 template <class T, bool kU>
-static RowSide<T, kU> row_sums(g2n_context* c, const int32_t* rows, const int32_t* cols, const T* data, uint64_t n,
-                               uint64_t n_rows, int side, int transposed, int64_t base = 0,
-                               int force_unsorted = -1) {
-  const int w = side;
-  using V = typename RowVal<T, kU>::type;
-  RowSide<T, kU> S{};
+static RowSorted<typename RowSumPolicy<T, kU>::E> row_sorted(g2n_context* c, const int32_t* rows, const int32_t* cols,
+                                                             const T* data, uint64_t n, uint64_t n_rows, int side,
+                                                             int transposed, int64_t base) {
+  using E = typename RowSumPolicy<T, kU>::E;
+  RowSorted<E> S{};
   auto* key_in = dget<uint32_t>(c, S_KEYS0, n);
   auto* key_out = dget<uint32_t>(c, S_KEYS1, n);
-  S.start = dget<uint32_t>(c, w ? S_RSTART1 : S_RSTART0, n_rows + 1);
-  S.ucnt = dget<uint32_t>(c, w ? S_UCNT1 : S_UCNT0, n_rows);
-  S.ocol = dget<uint32_t>(c, w ? S_ROUT1 : S_ROUT0, n);
-  S.oval = dget<V>(c, w ? S_RVAL1 : S_RVAL0, n);
-  auto* rowflag = dget<uint8_t>(c, w ? S_RFLAG1 : S_RFLAG0, n_rows);
-  PV<T>* pv_out = nullptr;
-  uint32_t* pc_out = nullptr;
-  void *scr_a = nullptr, *scr_b = nullptr;  // long-row merge scratch: buffers the sort no longer needs
-  G2N_HIP(hipMemsetAsync(rowflag, 0, n_rows ? n_rows : 1, c->stream));
-  const int bits = bits_for(n_rows);
+  S.start = dget<uint32_t>(c, side ? S_RSTART1 : S_RSTART0, n_rows + 1);
   if (n) {
-    if (kU) {
-      auto* pc_in = dget<uint32_t>(c, S_VALS0, n);
-      pc_out = dget<uint32_t>(c, S_VALS1, n);
-      if (base == 0) {  // the coordinates are the sort's input as they are (rocPRIM leaves inputs intact)
-        const uint32_t* r = (const uint32_t*)rows;
-        const uint32_t* q = (const uint32_t*)cols;
-        sort_pairs_u32<uint32_t>(c, transposed ? q : r, key_out, transposed ? r : q, pc_out, n, bits);
+    auto* in = dget<E>(c, S_VALS0, n);
+    auto* out = dget<E>(c, S_VALS1, n);
+    const uint32_t* key = key_in;
+    const E* val = in;
+    if constexpr (kU) {
+      if (base == 0) {  // the coordinates are the sort's input as they are (the sort leaves inputs intact)
+        key = (const uint32_t*)(transposed ? cols : rows);
+        val = (const uint32_t*)(transposed ? rows : cols);
       } else {
         hipLaunchKernelGGL((k_pack<T, true>), dim3(grid_for(n)), dim3(kTPB), 0, c->stream, rows, cols, data, n,
-                           transposed, base, key_in, (PV<T>*)nullptr, pc_in);
-        sort_pairs_u32<uint32_t>(c, key_in, key_out, pc_in, pc_out, n, bits);
+                           transposed, base, key_in, (PV<T>*)nullptr, in);
       }
-      scr_a = key_in;
-      scr_b = pc_in;
+      S.scr_a = key_in;
+      S.scr_b = in;
     } else {
-      auto* pv_in = dget<PV<T>>(c, S_VALS0, n);
-      pv_out = dget<PV<T>>(c, S_VALS1, n);
       hipLaunchKernelGGL((k_pack<T, false>), dim3(grid_for(n)), dim3(kTPB), 0, c->stream, rows, cols, data, n,
-                         transposed, base, key_in, pv_in, (uint32_t*)nullptr);
-      sort_pairs_u32<PV<T>>(c, key_in, key_out, pv_in, pv_out, n, bits);
-      scr_a = pv_in;
-      scr_b = dget<PV<T>>(c, S_RSCR, n);
+                         transposed, base, key_in, in, (uint32_t*)nullptr);
+      S.scr_a = in;
+      S.scr_b = dget<E>(c, S_RSCR, n);
     }
+    sort_pairs_u32<E>(c, key, key_out, val, out, n, bits_for(n_rows));
+    S.in = out;
   }
   G2N_HIP(hipMemsetAsync(&c->ctl->row_gap, 0, sizeof(unsigned long long), c->stream));
   hipLaunchKernelGGL(k_row_bounds, dim3(grid_for(n + 1)), dim3(kTPB), 0, c->stream, key_out, n, n_rows, S.start,
                      c->ctl);
   hipLaunchKernelGGL(k_row_start, dim3(grid_for(n_rows + 1)), dim3(kTPB), 0, c->stream, key_out, n, n_rows, S.start,
                      (const Ctl*)c->ctl);
+  return S;
+}
+
+// k_row_finish<P> over sorted rows into side's per-row buffers (rowflag: null for a policy that
+// reports nothing).
+template <class P, class T, bool kU>
+static RowSide<T, kU> finish_rows(g2n_context* c, const RowSorted<typename P::E>& in, uint64_t n, uint64_t n_rows,
+                                  int side, uint8_t* rowflag) {
+  RowSide<T, kU> S{};
+  S.start = in.start;
+  S.ucnt = dget<uint32_t>(c, side ? S_UCNT1 : S_UCNT0, n_rows);
+  S.ocol = dget<uint32_t>(c, side ? S_ROUT1 : S_ROUT0, n);
+  S.oval = dget<typename P::V>(c, side ? S_RVAL1 : S_RVAL0, n);
   if (n_rows)
-    hipLaunchKernelGGL((k_row_sum<T, kU>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, S.start, n_rows, pv_out,
-                       pc_out, S.ocol, S.oval, scr_a, scr_b, S.ucnt, rowflag, c->ctl, w);
+    hipLaunchKernelGGL((k_row_finish<P>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream,
+                       (const uint32_t*)S.start, n_rows, in.in, S.ocol, S.oval, in.scr_a, in.scr_b, S.ucnt, rowflag,
+                       c->ctl, side);
+  return S;
+}
+
+// coo.tocsr() of one orientation (transposed: of A.T), up to the per-row sorted unique entries.
+// side, transposed, base: as row_sorted; force_unsorted: -1 = this matrix decides scipy's global
+// has_sorted_indices, else the caller's verdict (sharded builds: the OR over all slices).
+template <class T, bool kU>
+static RowSide<T, kU> row_sums(g2n_context* c, const int32_t* rows, const int32_t* cols, const T* data, uint64_t n,
+                               uint64_t n_rows, int side, int transposed, int64_t base = 0,
+                               int force_unsorted = -1) {
+  auto* rowflag = dget<uint8_t>(c, side ? S_RFLAG1 : S_RFLAG0, n_rows);
+  G2N_HIP(hipMemsetAsync(rowflag, 0, n_rows ? n_rows : 1, c->stream));
+  const auto sorted = row_sorted<T, kU>(c, rows, cols, data, n, n_rows, side, transposed, base);
+  RowSide<T, kU> S = finish_rows<RowSumPolicy<T, kU>, T, kU>(c, sorted, n, n_rows, side, rowflag);
   sync_ctl(c);
-  S.local_unsorted = c->h_ctl->unsorted[w] != 0;
+  S.local_unsorted = c->h_ctl->unsorted[side] != 0;
   S.unsorted = force_unsorted >= 0 ? force_unsorted != 0 : S.local_unsorted;
-  S.flagged = c->h_ctl->flagged[w] != 0;
+  S.flagged = c->h_ctl->flagged[side] != 0;
   if constexpr (!kU) {
     if (n && S.unsorted && S.flagged) {  // scipy std::sort-ed these rows: redo them exactly
       auto* kv = dget<KV<int32_t, T>>(c, S_KV, n);
       hipLaunchKernelGGL((k_row_emulate<T>), dim3(grid_for(n_rows, 64)), dim3(64), 0, c->stream, S.start, n_rows,
-                         rowflag, pv_out, S.ocol, S.oval, kv);
+                         rowflag, sorted.in, S.ocol, S.oval, kv);
     }
   }
   return S;
@@ -907,58 +931,72 @@ static bool csr_partition_w(g2n_context* c, const int32_t* rows, const int32_t* 
   return true;
 }
 
+static int32_t* csr_indptr(g2n_context* c, uint64_t n_rows, g2n_result* R) {
+  auto* indptr = dget<int32_t>(c, S_INDPTR, n_rows + 1);
+  if (n_rows == 0) G2N_HIP(hipMemsetAsync(indptr, 0, sizeof(int32_t), c->stream));
+  R->format = G2N_FMT_CSR;
+  R->indptr = indptr;
+  return indptr;
+}
+
+// The CSR of one side's per-row unique entries (of at most n_entries): scan of the rows' counts, compaction.
+template <class T, bool kU>
+static void finish_sum_rows(g2n_context* c, const RowSide<T, kU>& A, uint64_t n_rows, uint64_t n_entries,
+                            g2n_result* R) {
+  auto* indptr = csr_indptr(c, n_rows, R);
+  auto* uoff = dget<uint32_t>(c, S_UOFF, n_rows);
+  excl_scan<uint32_t>(c, A.ucnt, uoff, n_rows);
+  auto* indices = dget<int32_t>(c, S_INDICES, n_entries);
+  T* odata = dget<T>(c, S_ODATA, n_entries);
+  if (n_rows) {
+    hipLaunchKernelGGL((k_row_compact<T, kU>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt, uoff,
+                       n_rows, A.ocol, A.oval, (T)1, indptr, indices, odata);
+    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, A.ucnt, uoff, n_rows, &c->ctl->n_keep);
+  }
+  R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
+  R->indices = indices;
+  R->data = odata;
+  phase(c, "csr");
+}
+
+// A.maximum(A.T) from A's and A.T's per-row unique entries (n_out: their sum at most): the rows'
+// merged counts, their scan, the merge again into place.
+template <class T, bool kU>
+static void finish_max_rows(g2n_context* c, const RowSide<T, kU>& A, const RowSide<T, kU>& B, uint64_t n_rows,
+                            uint64_t n_out, g2n_result* R) {
+  auto* indptr = csr_indptr(c, n_rows, R);
+  auto* mcnt = dget<uint32_t>(c, S_MCNT, n_rows);
+  auto* moff = dget<uint32_t>(c, S_MOFF, n_rows);
+  auto* indices = dget<int32_t>(c, S_INDICES, n_out);
+  T* odata = dget<T>(c, S_ODATA, n_out);
+  if (n_rows) {
+    hipLaunchKernelGGL((k_row_max<T, kU, false>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
+                       A.ocol, A.oval, B.start, B.ucnt, B.ocol, B.oval, (T)1, n_rows, mcnt, (const uint32_t*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr, (T*)nullptr);
+    excl_scan<uint32_t>(c, mcnt, moff, n_rows);
+    hipLaunchKernelGGL((k_row_max<T, kU, true>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
+                       A.ocol, A.oval, B.start, B.ucnt, B.ocol, B.oval, (T)1, n_rows, mcnt, moff, indptr, indices,
+                       odata);
+    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, mcnt, moff, n_rows, &c->ctl->n_keep);
+  }
+  R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
+  R->indices = indices;
+  R->data = odata;
+  phase(c, "maxsym");
+}
+
 // LAST: the weighted CSR of the graph parse_gfa(build_graph=True, weight_tag=T) builds, from the
 // stream-order triplets of an asymmetric float64 build whose untagged records carry kWNone
-// (ParseOpts::w_last).  row_sums' weighted leg up to the rows' bounds — k_pack, the stable radix sort
-// by row —, then k_row_last per row and SUM's compaction.  Nothing here depends on scipy's order.
+// (ParseOpts::w_last).  The row path with the Last policy in place of Sum<double>, then SUM's
+// compaction.  Nothing here depends on scipy's order.
 static void csr_last(g2n_context* c, const int32_t* rows, const int32_t* cols, const double* data, uint64_t n,
                      uint64_t n_rows, g2n_result* R) {
   if (n >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "more than 2^31-1 weighted matrix entries");
-  auto* key_in = dget<uint32_t>(c, S_KEYS0, n);
-  auto* key_out = dget<uint32_t>(c, S_KEYS1, n);
-  auto* start = dget<uint32_t>(c, S_RSTART0, n_rows + 1);
-  auto* ucnt = dget<uint32_t>(c, S_UCNT0, n_rows);
-  auto* ocol = dget<uint32_t>(c, S_ROUT0, n);
-  auto* oval = dget<double>(c, S_RVAL0, n);
-  PV<double>* pv_out = nullptr;
-  void *scr_a = nullptr, *scr_b = nullptr;
-  if (n) {
-    auto* pv_in = dget<PV<double>>(c, S_VALS0, n);
-    pv_out = dget<PV<double>>(c, S_VALS1, n);
-    hipLaunchKernelGGL((k_pack<double, false>), dim3(grid_for(n)), dim3(kTPB), 0, c->stream, rows, cols, data, n, 0,
-                       (int64_t)0, key_in, pv_in, (uint32_t*)nullptr);
-    sort_pairs_u32<PV<double>>(c, key_in, key_out, pv_in, pv_out, n, bits_for(n_rows));
-    scr_a = pv_in;  // the long rows' merge scratch: buffers the sort no longer needs
-    scr_b = dget<PV<double>>(c, S_RSCR, n);
-  }
-  G2N_HIP(hipMemsetAsync(&c->ctl->row_gap, 0, sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(k_row_bounds, dim3(grid_for(n + 1)), dim3(kTPB), 0, c->stream, key_out, n, n_rows, start, c->ctl);
-  hipLaunchKernelGGL(k_row_start, dim3(grid_for(n_rows + 1)), dim3(kTPB), 0, c->stream, key_out, n, n_rows, start,
-                     (const Ctl*)c->ctl);
-  if (n_rows)
-    hipLaunchKernelGGL(k_row_last, dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, (const uint32_t*)start, n_rows,
-                       (const PV<double>*)pv_out, ocol, oval, scr_a, scr_b, ucnt);
+  const auto sorted = row_sorted<double, false>(c, rows, cols, data, n, n_rows, 0, 0, 0);
+  const RowSide<double, false> A = finish_rows<RowLast, double, false>(c, sorted, n, n_rows, 0, nullptr);
   phase(c, "last");
-  auto* indptr = dget<int32_t>(c, S_INDPTR, n_rows + 1);
-  if (n_rows == 0) G2N_HIP(hipMemsetAsync(indptr, 0, sizeof(int32_t), c->stream));
-  auto* uoff = dget<uint32_t>(c, S_UOFF, n_rows);
-  excl_scan<uint32_t>(c, ucnt, uoff, n_rows);
-  auto* indices = dget<int32_t>(c, S_INDICES, n);
-  auto* odata = dget<double>(c, S_ODATA, n);
-  if (n_rows) {
-    hipLaunchKernelGGL((k_row_compact<double, false>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream,
-                       (const uint32_t*)start, (const uint32_t*)ucnt, (const uint32_t*)uoff, n_rows,
-                       (const uint32_t*)ocol, (const double*)oval, 1.0, indptr, indices, odata);
-    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, ucnt, uoff, n_rows, &c->ctl->n_keep);
-  }
-  R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
-  R->format = G2N_FMT_CSR;
-  R->indptr = indptr;
-  R->indices = indices;
-  R->data = odata;
-  R->sum_sorted = -1;  // not computed: a LAST cell does not depend on scipy's order
-  R->sum_t_sorted = -1;
-  phase(c, "csr");
+  finish_sum_rows<double, false>(c, A, n_rows, n, R);
+  R->sum_sorted = R->sum_t_sorted = -1;  // not computed: a LAST cell does not depend on scipy's order
 }
 
 template <class T, bool kU>
@@ -979,53 +1017,16 @@ static void assemble_t(g2n_context* c, const int32_t* rows, const int32_t* cols,
   }
   // the row-sum path (weighted / float sums, or a partition that declined) keeps int32 positions
   if (n_trip >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "more than 2^31-1 weighted matrix entries");
-  const T one = (T)1;
   // (force_unsorted >= 0: a row band of a larger COO, g2n_coo_to_csr_band — scipy's verdict is the whole
   // matrix's; sum_sorted still reports this band's own)
   RowSide<T, kU> A = row_sums<T, kU>(c, rows, cols, data, n_trip, n_rows, 0, 0, 0, force_unsorted);
   R->sum_sorted = A.local_unsorted ? 0 : 1;
   phase(c, "sum");
-  auto* indptr = dget<int32_t>(c, S_INDPTR, n_rows + 1);
-  if (n_rows == 0) G2N_HIP(hipMemsetAsync(indptr, 0, sizeof(int32_t), c->stream));
-  R->format = G2N_FMT_CSR;
-  R->indptr = indptr;
-  if (!maxsym) {
-    auto* uoff = dget<uint32_t>(c, S_UOFF, n_rows);
-    excl_scan<uint32_t>(c, A.ucnt, uoff, n_rows);
-    auto* indices = dget<int32_t>(c, S_INDICES, n_trip);
-    T* odata = dget<T>(c, S_ODATA, n_trip);
-    if (n_rows) {
-      hipLaunchKernelGGL((k_row_compact<T, kU>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
-                         uoff, n_rows, A.ocol, A.oval, one, indptr, indices, odata);
-      hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, A.ucnt, uoff, n_rows, &c->ctl->n_keep);
-    }
-    R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
-    R->indices = indices;
-    R->data = odata;
-    phase(c, "csr");
-    return;
-  }
+  if (!maxsym) return finish_sum_rows<T, kU>(c, A, n_rows, n_trip, R);
   // A.maximum(A.T): B = SUM(A) above, BT = SUM(A.T) with A.T's own scatter order
   RowSide<T, kU> B = row_sums<T, kU>(c, rows, cols, data, n_trip, n_cols, 1, 1);
   phase(c, "sum_t");
-  auto* mcnt = dget<uint32_t>(c, S_MCNT, n_rows);
-  auto* moff = dget<uint32_t>(c, S_MOFF, n_rows);
-  auto* indices = dget<int32_t>(c, S_INDICES, 2 * n_trip);
-  T* odata = dget<T>(c, S_ODATA, 2 * n_trip);
-  if (n_rows) {
-    hipLaunchKernelGGL((k_row_max<T, kU, false>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
-                       A.ocol, A.oval, B.start, B.ucnt, B.ocol, B.oval, one, n_rows, mcnt, (const uint32_t*)nullptr,
-                       (int32_t*)nullptr, (int32_t*)nullptr, (T*)nullptr);
-    excl_scan<uint32_t>(c, mcnt, moff, n_rows);
-    hipLaunchKernelGGL((k_row_max<T, kU, true>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
-                       A.ocol, A.oval, B.start, B.ucnt, B.ocol, B.oval, one, n_rows, mcnt, moff, indptr, indices,
-                       odata);
-    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, mcnt, moff, n_rows, &c->ctl->n_keep);
-  }
-  R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
-  R->indices = indices;
-  R->data = odata;
-  phase(c, "maxsym");
+  finish_max_rows<T, kU>(c, A, B, n_rows, 2 * n_trip, R);
 }
 
 // The CSR row slice [base, base + n_rows) of a sharded build from its routed triplet streams:
@@ -1051,53 +1052,16 @@ static void assemble_pair_t(g2n_context* c, const int32_t* ar, const int32_t* ac
       return;
     }
   }
-  const T one = (T)1;
   RowSide<T, kU> A = row_sums<T, kU>(c, ar, ac, ad, an, n_rows, 0, 0, base,
                                      force_unsorted < 0 ? -1 : (force_unsorted & 1));
   R->sum_sorted = A.local_unsorted ? 0 : 1;
   phase(c, "sum");
-  auto* indptr = dget<int32_t>(c, S_INDPTR, n_rows + 1);
-  if (n_rows == 0) G2N_HIP(hipMemsetAsync(indptr, 0, sizeof(int32_t), c->stream));
-  R->format = G2N_FMT_CSR;
-  R->indptr = indptr;
-  if (!maxsym) {
-    auto* uoff = dget<uint32_t>(c, S_UOFF, n_rows);
-    excl_scan<uint32_t>(c, A.ucnt, uoff, n_rows);
-    auto* indices = dget<int32_t>(c, S_INDICES, an);
-    T* odata = dget<T>(c, S_ODATA, an);
-    if (n_rows) {
-      hipLaunchKernelGGL((k_row_compact<T, kU>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
-                         uoff, n_rows, A.ocol, A.oval, one, indptr, indices, odata);
-      hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, A.ucnt, uoff, n_rows, &c->ctl->n_keep);
-    }
-    R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
-    R->indices = indices;
-    R->data = odata;
-    phase(c, "csr");
-    return;
-  }
+  if (!maxsym) return finish_sum_rows<T, kU>(c, A, n_rows, an, R);
   RowSide<T, kU> B = row_sums<T, kU>(c, tr, tc, td, tn, n_rows, 1, 0, base,
                                      force_unsorted < 0 ? -1 : ((force_unsorted >> 1) & 1));
   R->sum_t_sorted = B.local_unsorted ? 0 : 1;
   phase(c, "sum_t");
-  auto* mcnt = dget<uint32_t>(c, S_MCNT, n_rows);
-  auto* moff = dget<uint32_t>(c, S_MOFF, n_rows);
-  auto* indices = dget<int32_t>(c, S_INDICES, an + tn);
-  T* odata = dget<T>(c, S_ODATA, an + tn);
-  if (n_rows) {
-    hipLaunchKernelGGL((k_row_max<T, kU, false>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
-                       A.ocol, A.oval, B.start, B.ucnt, B.ocol, B.oval, one, n_rows, mcnt, (const uint32_t*)nullptr,
-                       (int32_t*)nullptr, (int32_t*)nullptr, (T*)nullptr);
-    excl_scan<uint32_t>(c, mcnt, moff, n_rows);
-    hipLaunchKernelGGL((k_row_max<T, kU, true>), dim3(grid_for(n_rows)), dim3(kTPB), 0, c->stream, A.start, A.ucnt,
-                       A.ocol, A.oval, B.start, B.ucnt, B.ocol, B.oval, one, n_rows, mcnt, moff, indptr, indices,
-                       odata);
-    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(1), 0, c->stream, mcnt, moff, n_rows, &c->ctl->n_keep);
-  }
-  R->nnz = n_rows ? (int64_t)read_dev(c, &c->ctl->n_keep) : 0;
-  R->indices = indices;
-  R->data = odata;
-  phase(c, "maxsym");
+  finish_max_rows<T, kU>(c, A, B, n_rows, an + tn, R);
 }
 
 template <class T>

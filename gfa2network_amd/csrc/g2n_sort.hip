@@ -3,7 +3,7 @@
 // Replaces the library sort under scipy's `coo_matrix.tocsr()` for weighted / float builds
 // (builders.py:281-283 -> scipy coo_tocsr + csr_sort_indices; utils.py:55 convert_format):
 // the triplets are ordered by row with the stream order kept inside each row, which is what
-// k_row_sum / k_row_emulate (g2n_kernels.hip) need to reproduce scipy's duplicate summation
+// k_row_finish / k_row_emulate (g2n_kernels.hip) need to reproduce scipy's duplicate summation
 // order.  Also the owner sort of the sharded key / triplet exchange when more ranks than the
 // stable owner partition handles.
 //

@@ -144,7 +144,7 @@ def _row(rng, n, length, distinct):
 
 
 def shape_records(scale: int = 1, seed: int = 7):
-    """(n, records (u, v, w)) holding every row shape of the LAST finish (g2n_kernels.hip k_row_last):
+    """(n, records (u, v, w)) holding every row shape of the LAST finish (g2n_kernels.hip k_row_finish<RowLast>):
     rows of 1, 2, 8, 9, 16, 17 and 33 triplets (both sides of the 8-wide network and of kRegRow = 16),
     rows whose columns arrive descending (12: the network sorts, 20: the merge runs), one cell 40 times
     inside a 60-entry row, a cell of untagged records only, a 256-row block of 9-entry rows (2304

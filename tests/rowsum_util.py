@@ -1,5 +1,5 @@
 """Case builders and references for the row-sum CSR path (k_pack, the LSD radix sort, k_row_bounds /
-k_row_start, k_row_sum, k_row_emulate, k_row_compact, k_row_max): COOs aimed at the constants those
+k_row_start, k_row_finish, k_row_emulate, k_row_compact, k_row_max): COOs aimed at the constants those
 kernels branch on, scipy as the reference, and the stable-order summation a case is told apart by.
 
 A Case is a COO (rows, cols in stream order; vals in its dtype, None for the uniform instance: every

@@ -1,4 +1,4 @@
-"""GPU: ``graph_matrix(path, weight_tag=...)`` — the LAST finish (g2n_kernels.hip k_row_last behind
+"""GPU: ``graph_matrix(path, weight_tag=...)`` — the LAST finish (g2n_kernels.hip k_row_finish<RowLast> behind
 g2n_graph_weights_from_path) — against a dict-overwrite loop over the records (graph_weight_util), on
 generated files that hold every row shape of the kernel, through each route the weight parse can
 take; and the weighted ``genome_distance_matrix`` over 73 paths (two search batches) against scipy's

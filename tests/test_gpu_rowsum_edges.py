@@ -1,5 +1,5 @@
 """The row-sum CSR path (TEST_NO_BUCKETS: k_pack, the stable LSD radix sort, k_row_bounds / k_row_start,
-k_row_sum with its register networks and merge sort, k_row_emulate over stl_sort.h, k_row_compact,
+k_row_finish (Count / Sum<T>) with its register networks and merge sort, k_row_emulate over stl_sort.h, k_row_compact,
 k_row_max) against scipy at the constants its kernels branch on (tests/rowsum_util.py builds the cases,
 tests/test_rowsum_cases.py shows on the CPU that they sit where they claim).  SUM: g2n_coo_to_csr on the
 arrays against coo.tocsr(); MAX-SYM: the COO as a GFA with RC:f weights against A.maximum(A.T).  indptr,
@@ -134,7 +134,7 @@ def test_twin_rows_16_and_17(gpu, dtype):
                          ids=["sum-u4096", "compact-u2048", "sum-w2048", "compact-w1024"])
 def test_staging_caps_sum(gpu, cap, uniform, tail):
     """256-row blocks holding cap - 1, cap and cap + 1 entries, staged beside direct, a ragged last block:
-    k_row_sum's caps (4096 uniform, 2048 weighted) and k_row_compact's (2048, 1024)."""
+    k_row_finish's caps (4096 uniform, 2048 weighted) and k_row_compact's (2048, 1024)."""
     for dtype in U.DTYPES:
         _sum(gpu, U.staging_case(cap, tail, dtype, uniform))
 

@@ -3,7 +3,8 @@
   * the hipEvent phase times of a LAST build (``graph_matrix``'s: g2n_graph_weights_from_path) beside
     the SUM build of the same file (the asymmetric float64 CSR with the same weight tag), on the
     largest weighted file ``bench.py --full`` generates (C3's bytes: 1 M S / 4 M L lines with an
-    ``RC:i:`` tag), each build once after one warm-up of each, through the same host entry;
+    ``RC:i:`` tag), the same SUM build forced onto the row path and the untagged (uniform) build forced
+    onto it, each build once after one warm-up of each, through the same host entry;
   * ``ms_search`` / ``ms_tables`` of the weighted mean tables with and without the seeded pass
     (G2N_DIST_MEAN_FOLD against G2N_DIST_MEAN) on a ring with chords, 512 paths of 8 steps.
 
@@ -40,7 +41,10 @@ def builds(tmp):
     nobuckets = lambda: nat.build_from_path(  # noqa: E731  (SUM through the stable row-sum path, LAST's skeleton)
         p, nat.make_options(directed=True, asymmetric=True, weight_tag="RC", output=nat.OUT_CSR, dtype="float64",
                             want_node_names=False, test_flags=nat.TEST_NO_BUCKETS))
-    for name, fn in (("last", last), ("sum", summed), ("sum_row_path", nobuckets)):
+    count = lambda: nat.build_from_path(  # noqa: E731  (the uniform SUM on the row path: the Count policy)
+        p, nat.make_options(directed=True, asymmetric=True, output=nat.OUT_CSR, dtype="float64",
+                            want_node_names=False, test_flags=nat.TEST_NO_BUCKETS))
+    for name, fn in (("last", last), ("sum", summed), ("sum_row_path", nobuckets), ("count_row_path", count)):
         fn()
         raw = fn()
         ph = phases(raw)
