@@ -28,7 +28,7 @@ E_ARG, E_IO, E_GZIP, E_DEVICE, E_NOMEM, E_UNSUPPORTED = 13, 14, 15, 16, 17, 18
 
 DTYPE_CODES = {"bool": 0, "int8": 1, "int32": 2, "float32": 3, "float64": 4}
 CODE_DTYPES = {v: np.dtype(k) for k, v in DTYPE_CODES.items()}
-OUT_PARSE, OUT_CSR, OUT_COO, OUT_EDGE_LIST = 0, 1, 2, 3
+OUT_PARSE, OUT_CSR, OUT_COO, OUT_EDGE_LIST, OUT_GRAPH_JSON = 0, 1, 2, 3, 4
 FMT_COO, FMT_CSR, FMT_TEXT = 0, 1, 2
 
 # every symbol include/g2n.h declares (tests check the library exports all of them)
@@ -519,7 +519,7 @@ def _from_result(ptr, rc: int) -> RawResult:
     out.n_cast_overflow = int(r.n_cast_overflow)
     out.input_bytes = int(r.input_bytes)
     if r.format == FMT_TEXT and r.data:
-        out.format = "text"  # export --format edge-list: the rendered lines (all, or those before a failure)
+        out.format = "text"  # export: the edge-list lines (all, or those before a failure) or the JSON document
         out.data = _view(r.data, r.nnz, np.uint8, owner)
     elif r.status == OK:
         idx = np.int32 if r.index_width == 4 else np.int64

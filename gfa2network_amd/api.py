@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
+           "save_npz", "export_edge_list", "export_graph_json", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
            "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
@@ -1344,6 +1344,52 @@ def export_edge_list(gfa, output="-", *, bidirected: bool = False, device: int =
     finally:
         if fh is not None:
             fh.close()
+
+
+_JSON_NODES_PREFIX = '{"directed": true, "multigraph": false, "graph": {}, "nodes": [{"id": '
+
+
+def export_graph_json(gfa, output="-", *, bidirected: bool = False, keep_directed_bidir: bool = False,
+                      raw_bytes_id: bool = False, device: int = 0) -> None:
+    """``gfa2network [--raw-bytes-id] export GFA --format json [--bidirected [--keep-directed-bidir]]
+    --output PATH`` (cli.py:282-306): ``json.dump(nx.node_link_data(G))`` of the graph
+    ``parse_gfa(GFA, build_graph=True, directed=True, ...)`` builds — a ``DiGraph``, with ``--bidirected``
+    a ``MultiGraph``, with ``--keep-directed-bidir`` too a ``MultiDiGraph`` — byte for byte, without a
+    graph object: the nodes in first-touch order, the links in NetworkX's adjacency order (a repeated
+    directed pair keeps its last record's orientations, a repeated multigraph pair counts its ``key``),
+    grouped, ordered and rendered on the GPU from the same parse as the matrix path
+    (``G2N_OUT_GRAPH_JSON``).  Sources as ``export_edge_list``: a named file, ``"-"`` (stdin) or a file
+    object; ``output`` a path or ``"-"`` (stdout).
+
+    As in the reference the graph is built before the output is opened: the one-shot warning comes first,
+    then any error of the build (the parser's, or the ASCII decode of a node key, whichever the stream
+    meets first) leaves no file.  With ``raw_bytes_id`` the keys stay ``bytes``, which ``json.dump``
+    cannot serialise: a graph with a node writes the document up to the first node's id and raises its
+    ``TypeError``.  NetworkX's own ``FutureWarning`` about ``node_link_data``'s ``edges=`` default is
+    not reproduced.  A file whose working set exceeds one GPU's free HBM raises ``NotImplementedError``.
+    """
+    src = gfa
+    if not hasattr(gfa, "read") and str(gfa) == "-":
+        src = io.BytesIO(sys.stdin.buffer.read())  # parser.py:104: sys.stdin.buffer, not gunzipped
+    if not hasattr(src, "read"):
+        _stats_one_piece(src, device, "export_graph_json", "convert_format")
+    opts = nat.make_options(bidirected=bidirected, keep_directed_bidir=keep_directed_bidir,
+                            want_node_names=not raw_bytes_id, output=nat.OUT_GRAPH_JSON, device=device)
+    raw = nat.build_from_buffer(src.read(), opts) if hasattr(src, "read") else nat.build_from_path(str(src), opts)
+    _graph_pass(raw, raw_bytes_id, False, gfa)
+    if raw_bytes_id and raw.n_nodes:
+        text = _JSON_NODES_PREFIX.encode()  # json.dump streams: what it wrote before it met the bytes key
+    else:
+        text = raw.data if raw.format == "text" and raw.data is not None else np.zeros(0, np.uint8)
+    if output != "-":
+        with open(output, "wb") as fh:  # cli.py:302-306: opened only once the graph exists
+            fh.write(memoryview(text))
+    else:
+        sys.stdout.flush()
+        sys.stdout.buffer.write(memoryview(text))
+        sys.stdout.buffer.flush()
+    if raw_bytes_id and raw.n_nodes:
+        raise TypeError("Object of type bytes is not JSON serializable")
 
 
 def _keep_index_dtype(M, raw):

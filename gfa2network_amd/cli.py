@@ -4,14 +4,15 @@ Same global flags (they precede the subcommand) and ``convert`` flags as
 gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backend, parse,
 ``convert_format``, ``save_matrix`` (dense guard -> SystemExit), then the
 ``<matrix>.nodes.tsv`` sidecar.  ``export --format edge-list`` (cli.py:264-281) renders its
-lines on the GPU from the same parse; ``stats`` (cli.py:152-159, 364-376) prints
+lines on the GPU from the same parse, ``export --format json`` (cli.py:282-306) the graph's node-link
+document (``export_graph_json``); ``stats`` (cli.py:152-159, 364-376) prints
 ``compute_stats``'s six numbers, taken on the GPU from the CSR; ``distance --path``, ``distance
 --seq`` and ``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same
 CSR (``--seq`` finds the nodes that carry the two sequences there too: ``sequence_distance``; an input
 that is no named file is a usage error, exit status 2, where the function raises the reference's
 FileNotFoundError).  As in
 the reference, ``distance`` and ``distance-matrix`` have no ``--weight-tag``: the functions take
-``weight_tag=``.  Graph outputs (``--graph``, export graphml / gexf / json) are outside the GPU
+``weight_tag=``.  Graph outputs (``--graph``, export graphml / gexf) are outside the GPU
 GFA->CSR path.
 """
 from __future__ import annotations
@@ -22,7 +23,7 @@ import sys
 from pathlib import Path
 
 from . import __version__
-from .api import (compute_stats, convert_format, export_edge_list, genome_distance, genome_distance_matrix, parse_gfa,
+from .api import (compute_stats, convert_format, export_edge_list, export_graph_json, genome_distance, genome_distance_matrix, parse_gfa,
                   parse_gfa_names, save_matrix, save_node_map_native, sequence_distance)
 
 
@@ -94,6 +95,11 @@ def main(argv: list[str] | None = None) -> None:
     parser = _parser()
     args = parser.parse_args(argv)
     if args.cmd == "export":
+        if args.format == "json":  # cli.py:282-306
+            export_graph_json(args.gfa, args.output, bidirected=args.bidirected,
+                              keep_directed_bidir=args.keep_directed_bidir, raw_bytes_id=args.raw_bytes_id,
+                              device=args.device)
+            return
         if args.format != "edge-list":
             parser.error(f"export --format {args.format} builds a NetworkX graph, outside the GPU GFA->CSR path")
         export_edge_list(args.gfa, args.output, bidirected=args.bidirected, device=args.device)

@@ -52,6 +52,9 @@ enum Slot {
   S_DTAB, S_DPP, S_DPN,  // g2n_csr_path_distances (g2n_dist.hip)
   S_WDIST, S_WVAL,  // g2n_csr_path_distances_weighted (g2n_wdist.hip)
   S_DFLAG, S_DKS, S_DSBLOB, S_DSOFFS, S_DIDS,  // g2n_distances_from_path: the step lookup
+  S_GJKEY, S_GJBCNT, S_GJBOFF, S_GJSTART, S_GJORI, S_GJCR, S_GJCC, S_GJIDX, S_GJK1, S_GJIDX1, S_GJK2, S_GJRS, S_GJPERM,
+  S_GJHEAD, S_GJHX, S_GJHS, S_GJFFLAG, S_GJFX, S_GJFGRP, S_GJLRS, S_GJORDER, S_GJCNT, S_GJBASE, S_GJGBASE, S_GJLS, S_GJLT,
+  S_GJLX, S_GJHEADSTR,  // G2N_OUT_GRAPH_JSON (g2n_graphjson.hip)
   S_QSTATE, S_QLINES, S_QNODE, S_QFPOS, S_QFLAG, S_QLAST, S_QCAND, S_QIDS, S_QBYTES, S_QNLEN, S_QNOFF, S_QNBLOB,  // g2n_seq_distance_from_path (g2n_seq.hip)
   S_NSLOTS
 };
@@ -2249,9 +2252,17 @@ static int run_edge_list(g2n_context* c, const uint8_t* in, uint64_t len, const 
   return R->status;
 }
 
+}  // namespace g2n
+
+// export --format json: the graph's node-link document, ordered and rendered in HBM (G2N_OUT_GRAPH_JSON)
+#include "g2n_graphjson.hip"
+
+namespace g2n {
+
 static int run_pipeline(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, g2n_result* R) {
   c->slots = GroupedCoo{};  // (set again only by a build whose COO result stays in group slots)
   if (o->output == G2N_OUT_EDGE_LIST) return run_edge_list(c, in, len, o, R);
+  if (o->output == G2N_OUT_GRAPH_JSON) return run_graph_json(c, in, len, o, R);
   return run_build(c, in, len, o, R);
 }
 

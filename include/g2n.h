@@ -29,6 +29,22 @@
  *                  err_detail = the key, and the text holds the lines written before it.
  *                  Parse errors (err_line >= 0) carry no text: the caller renders the
  *                  input's prefix [0, start of err_line) to reproduce the partial output.
+ *   G2N_OUT_GRAPH_JSON  the bytes `gfa2network export --format json [--bidirected
+ *                  [--keep-directed-bidir]]` writes (cli.py:282-306): json.dump of
+ *                  nx.node_link_data(G) for the DiGraph / MultiGraph / MultiDiGraph that
+ *                  parse_gfa(build_graph=True, directed=True, ...) builds: nodes in first-touch
+ *                  order, links in NetworkX's adjacency order.  `bidirected` and
+ *                  `keep_directed_bidir` select the class; `want_node_names` = 0 is
+ *                  --raw-bytes-id.  Result format G2N_FMT_TEXT: data = the document, nnz = its
+ *                  length.  The reference builds the graph before it opens its output, so a
+ *                  failed build carries no text.  With str keys (want_node_names = 1) a node key
+ *                  with a byte >= 0x80 is G2N_E_UNICODE with err_line = -1, err_index = the node
+ *                  id and err_detail = the key (the graph path decodes keys as ASCII); it wins
+ *                  over a parse error on a later line, and has_warning is set only when the
+ *                  unsupported record precedes the key's first touch.  With bytes keys a graph
+ *                  that has a node carries no text (data = NULL, n_nodes > 0): json.dump writes
+ *                  up to the first node's id and raises TypeError.  Limits: fewer than 2^32 - 1
+ *                  entries (add_edge calls) and 2^31 - 1 nodes, else G2N_E_UNSUPPORTED.
  *
  * Errors: a non-zero status is one of G2N_E_*; each maps 1:1 to the exception the
  * reference raises for the same input (type + message; the Python shim re-raises it).
@@ -75,7 +91,7 @@ enum {
 /* ---- matrix dtypes (cli.py:92-97 --dtype choices) ------------------------------------ */
 enum { G2N_BOOL = 0, G2N_INT8 = 1, G2N_INT32 = 2, G2N_FLOAT32 = 3, G2N_FLOAT64 = 4 };
 
-enum { G2N_OUT_PARSE = 0, G2N_OUT_CSR = 1, G2N_OUT_COO = 2, G2N_OUT_EDGE_LIST = 3 };
+enum { G2N_OUT_PARSE = 0, G2N_OUT_CSR = 1, G2N_OUT_COO = 2, G2N_OUT_EDGE_LIST = 3, G2N_OUT_GRAPH_JSON = 4 };
 enum { G2N_FMT_COO = 0, G2N_FMT_CSR = 1, G2N_FMT_TEXT = 2 };
 
 /* Mirrors parse_gfa's keyword arguments that affect the matrix (builders.py:30-50). */
