@@ -115,7 +115,6 @@ struct g2n_context {
   g2n::GroupedCoo gcoo;       // the current build's COO, when it went to group slots
   g2n::GroupedCoo slots;      // the last build's COO result when it stayed in group slots (G2N_RANGE_SLOTS)
   const uint32_t* wenc = nullptr;  // the current build's values as exact-int32 codes (k_values), if written
-  bool no_group = false;      // redo of a build whose group-slot COO the partition refused
   g2n::ScanSlot scan_slot[g2n::S_NSLOTS];  // scan_excl's per-slot epoch / ticket state
   bool edge_text = false;     // run_edge_list's build: decimal names are left to the text render
   bool names_dec = false;     // ... and that build's names were the decimal ids (no blob written)
@@ -333,6 +332,8 @@ static size_t dtype_size(int dt) {
     default: return 8;
   }
 }
+template <class F>
+static void with_dtype(int dt, F&& f);  // f(T{}), T the dtype's element type (g2n_queries.hip)
 
 // ------------------------------------------------- SUM (coo.tocsr) on device -------
 template <class T, bool kU>
@@ -1357,6 +1358,147 @@ static bool first_segment_pattern(g2n_context* c, const uint8_t* in, uint64_t le
   return false;
 }
 
+// What one build is, decided before its first launch: everything the options, the test flags, the
+// context's mode flags and the input's size give.  make_plan fills it once; each fact has one name.
+struct BuildPlan {
+  bool bidir, keep, strip;
+  bool gd;             // one triplet per edge line and orientation (builders.py:143)
+  bool maxsym;         // the result is A.maximum(A.T) (builders.py:282)
+  uint32_t tps, tpe;   // touches per S line / per edge line
+  uint32_t ktrip;      // triplets per edge line
+  int dt;
+  uint64_t n_tiles;
+  bool names;          // options.want_node_names
+  // options.range_flags G2N_RANGE_DECIMAL: one byte range of a sharded build whose node ids are decimal and
+  // GLOBAL: s_base S lines precede the range, n_seg_all S lines in the whole file (the caller checked across
+  // ranges that no edge line precedes an S line).  Lean parse or nothing.
+  bool shard_dec;
+  // g2n_build_decimal_range: the S lines before the range are not known yet — the one-pass parse reports
+  // the range's offset evidence instead of checking it (the caller checks across ranges)
+  bool shard_deferred;
+  uint64_t s_base, n_seg_all;  // (0 / 0 for a whole file)
+  // a sharded decimal range whose caller takes the COO as group slots (G2N_RANGE_SLOTS: unweighted,
+  // coordinates only — its route or slice CSR needs no stream order)
+  bool slots_out;
+  // G2N_RANGE_NO_VALUES: a sharded range whose caller routes coordinates only (uniform values, no COO
+  // result): the values array is left unwritten
+  bool no_values;
+  // a LAST build (the graph's weighted CSR): per-edge weights in stream order, records without a numeric
+  // tag marked (kWNone) — never group slots, never codes
+  bool last;
+  bool coo_out;        // the result is the stream-order COO itself (builders.py:281)
+  bool no_group;       // the redo of a build whose group-slot COO the partition refused
+  // group slots when the COO's only reader is the bucket partition (a CSR output), or slots_out
+  bool grouped;
+  bool has_wt;
+  const char* weight_tag;
+  uint32_t wt_len;
+  uint64_t wt_pack;    // the weight tag's first 8 bytes, little-endian
+  // bidirected keys / one integer weight tag: the lean front ends' extended instances (k_tile_lean kExt),
+  // tile-local for whole files with a tag of at most 8 bytes
+  bool ext, ext_ok;
+  // a weighted SUM CSR in dtypes whose cast of a canonical <= 9-digit integer can neither fail nor lose
+  // the integer's exact-int32 code (float32: the code of the rounded value) takes group slots: the parse
+  // writes the codes, so neither k_tile_compact nor k_values runs (C3); a bucket partition that declines
+  // (an overfull bucket, an inexact float sum) redoes the build without groups
+  bool codes_in_parse;
+};
+
+static BuildPlan make_plan(const g2n_context* c, const g2n_options* o, uint64_t len, bool no_group) {
+  BuildPlan P{};
+  P.bidir = o->bidirected != 0;
+  P.keep = o->keep_directed_bidir != 0;
+  P.strip = o->strip_orientation != 0;
+  P.gd = P.keep || (!P.bidir && o->directed != 0);
+  P.maxsym = P.gd && !o->asymmetric;
+  P.tps = P.bidir ? 2 : 1;
+  P.tpe = (P.bidir && !P.keep) ? 4 : 2;
+  P.ktrip = P.tpe == 4 ? 4u : (P.gd ? 1u : 2u);
+  P.dt = o->dtype;
+  P.n_tiles = (len + kTile - 1) / kTile;
+  P.names = o->want_node_names != 0;
+  P.weight_tag = o->weight_tag;
+  P.wt_len = o->weight_tag ? (uint32_t)std::strlen(o->weight_tag) : 0u;
+  P.has_wt = P.wt_len > 0;
+  for (uint32_t k = 0; k < P.wt_len && k < 8; k++) P.wt_pack |= (uint64_t)(uint8_t)o->weight_tag[k] << (8 * k);
+  P.shard_dec = (o->range_flags & G2N_RANGE_DECIMAL) != 0;
+  P.shard_deferred = P.shard_dec && (o->range_flags & G2N_RANGE_EVIDENCE) != 0;
+  P.last = c->last_build;
+  if (P.last && !(P.has_wt && P.dt == G2N_FLOAT64 && o->output == G2N_OUT_CSR && o->asymmetric && !P.bidir &&
+                  !P.shard_dec))
+    throw Failure(G2N_E_ARG, "the graph's weighted CSR: a plain float64 CSR build with a weight tag");
+  if (P.shard_dec && (o->output != G2N_OUT_COO || P.names || o->range_s_base < 0 || o->range_n_segments < 0))
+    throw Failure(G2N_E_ARG, "sharded decimal-id build: output COO without names, s_base / n_seg >= 0");
+  P.s_base = P.shard_dec ? (uint64_t)o->range_s_base : 0;
+  P.n_seg_all = P.shard_dec ? (uint64_t)o->range_n_segments : 0;
+  P.no_values = !P.has_wt && (o->range_flags & G2N_RANGE_NO_VALUES) != 0;
+  P.slots_out = P.shard_dec && (o->range_flags & G2N_RANGE_SLOTS) && !P.bidir && P.no_values;
+  P.coo_out = (o->output == G2N_OUT_PARSE && !P.maxsym) || o->output == G2N_OUT_COO;
+  P.no_group = no_group;
+  P.grouped = (!P.coo_out || P.slots_out) && !no_group && !P.last && !(c->test_flags & (kTestNoBuckets | kTestNoGroup));
+  P.ext = P.bidir || P.has_wt;
+  P.ext_ok = !P.shard_dec && P.wt_len <= 8 && !(c->test_flags & kTestNoExtLean);
+  P.codes_in_parse = P.has_wt && P.grouped && !P.maxsym && o->output == G2N_OUT_CSR &&
+                     (P.dt == G2N_FLOAT64 || P.dt == G2N_FLOAT32 || P.dt == G2N_INT32);
+  return P;
+}
+
+// the parse's view of the plan (k_tile_parse, k_tile_lean): orientation keys, the weight tag, a LAST build's mark
+static ParseOpts plan_parse_opts(const BuildPlan& P) {
+  ParseOpts op{};
+  op.bidir = P.bidir;
+  op.keep = P.keep;
+  op.strip = P.strip;
+  op.has_wt = P.has_wt;
+  op.wt_len = P.wt_len;
+  op.wt_pack = P.wt_pack;
+  op.w_last = P.last ? 1u : 0u;
+  return op;
+}
+
+// The TileCnt scan behind a count pass: chunk sums, the total (device; returned) and — tbase given — every
+// tile's exclusive base.
+static const TileCnt* scan_tile_counts(g2n_context* c, const TileCnt* tcnt, uint64_t n_tiles, TileCnt* tbase) {
+  const uint64_t n_parts = (n_tiles + kStructChunk - 1) / kStructChunk;
+  auto* part = dget<TileCnt>(c, S_TEMP, n_parts + 1);  // chunk sums, then the total
+  hipLaunchKernelGGL(k_struct_reduce<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream, tcnt, n_tiles, part);
+  hipLaunchKernelGGL(k_struct_scan_parts<TileCnt>, dim3(1), dim3(256), 0, c->stream, part, n_parts, part + n_parts);
+  if (tbase)
+    hipLaunchKernelGGL(k_struct_scan_chunks<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream, tcnt, n_tiles,
+                       (const TileCnt*)part, tbase);
+  return part + n_parts;
+}
+
+// Every k_tile_lean launch: (kMode, grouped, ext) -> the instantiation, one block per tile (kLeanDecimal) or per
+// entry of H.tlist.  A diagnostics build (-DG2N_K2_STAMPS) points the kernel at a cleared stamps buffer first
+// and, stamps_env given, writes the stamps to the file that variable names.
+template <int kMode>
+static void launch_tile_lean(g2n_context* c, const uint8_t* in, uint64_t len, uint64_t n_blocks, bool grouped, bool ext,
+                             const ParseOpts& po, TileCnt* tcnt, TileLean* tlean, uint32_t* gcount, uint64_t gcap,
+                             const HashLeanArgs& H, const char* stamps_env = nullptr) {
+#ifdef G2N_K2_STAMPS
+  const uint64_t n_stamps = (len + kTile - 1) / kTile * kK2Stamps;
+  unsigned long long* stamps = dget<unsigned long long>(c, S_TEMP, n_stamps);
+  G2N_HIP(hipMemsetAsync(stamps, 0, n_stamps * 8, c->stream));
+  G2N_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g2n_k2_stamps), &stamps, sizeof(stamps), 0, hipMemcpyHostToDevice,
+                                 c->stream));
+#endif
+  void (*kernel)(const uint8_t*, uint64_t, ParseOpts, Ctl*, TileCnt*, TileLean*, uint32_t*, uint64_t, HashLeanArgs);
+  if constexpr (kMode == kLeanDecimal) {
+    if (ext) kernel = grouped ? k_tile_lean<kMode, true, true> : k_tile_lean<kMode, false, true>;
+    else kernel = grouped ? k_tile_lean<kMode, true> : k_tile_lean<kMode, false>;
+  } else if constexpr (kMode == kLeanEdges || kMode == kLeanDirEdges) {
+    kernel = ext ? k_tile_lean<kMode, false, true> : k_tile_lean<kMode, false>;
+  } else {
+    kernel = k_tile_lean<kMode, false>;
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_blocks), dim3(kLeanTPB), 0, c->stream, in, len, po, c->ctl, tcnt, tlean,
+                     grouped ? gcount : nullptr, grouped ? gcap : (uint64_t)0, H);
+#ifdef G2N_K2_STAMPS
+  if (stamps_env) stamps_to_file(c, stamps_env, stamps, n_stamps);
+#endif
+}
+
 // The lean decimal-id parse in one pass over the input, without K1: every tile parses with
 // tile-local positions, writes its COO to a slot of kTileEdgeCap edges and its own counts
 // (k_tile_lean with ParseOpts.tile_pad); one scan of those counts gives the tile bases, a check
@@ -1367,20 +1509,19 @@ static bool first_segment_pattern(g2n_context* c, const uint8_t* in, uint64_t le
 // slot): the caller then runs K1 and the classic parse, as if this had not run.
 constexpr uint32_t kTileEdgeCap = (uint32_t)(kTile / 12) + 6;  // a lean edge line is at least 12 bytes (2736 for 32 KiB)
 
-// grouped: the COO goes to group slots instead (k_tile_lean<true>, GroupedCoo) and is not compacted
-// — for builds whose only consumer is the unweighted bucket partition.
-// s_base / n_seg_all: a byte range of a sharded file with global decimal ids (options.range_s_base / range_n_segments):
-// the S lines before the range and in the whole file; 0 / 0 for a whole file.
-// xo (the extended instance, k_tile_lean kExt): bidirected keys and / or one integer weight tag —
-// bidir / keep / has_wt / wt_len / wt_pack read from it; the per-edge weights go to S_EW in stream
-// order beside the compacted COO (never group slots).
-static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, uint64_t n_tiles, uint32_t ktrip,
-                             TileCnt* tcnt, TileCnt* tbase, TileCnt* tot_out, bool grouped, uint64_t s_base = 0,
-                             uint64_t n_seg_all = 0, bool deferred = false, const ParseOpts* xo = nullptr,
-                             bool warn_ok = false, uint64_t dpre = 0, uint32_t dpre_len = 0) {
-  // an extended build takes group slots when its only reader is the bucket partition: unweighted, or
-  // a weighted SUM CSR whose codes the parse writes (xo->wenc set by the caller as a flag)
-  if (xo && xo->has_wt && !xo->wenc) grouped = false;
+// P.grouped: the COO goes to group slots instead (k_tile_lean<true>, GroupedCoo) and is not compacted
+// — for builds whose only consumer is the bucket partition.
+// P.s_base / P.n_seg_all: a byte range of a sharded file with global decimal ids.
+// P.ext (the extended instance, k_tile_lean kExt): bidirected keys and / or one integer weight tag; the
+// per-edge weights go to S_EW in stream order beside the compacted COO (never group slots).
+// dpre / dpre_len: names behind one constant prefix (first_segment_prefixed).
+static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, const BuildPlan& P, TileCnt* tcnt,
+                             TileCnt* tbase, TileCnt* tot_out, uint64_t dpre, uint32_t dpre_len) {
+  const uint64_t n_tiles = P.n_tiles;
+  const uint32_t ktrip = P.ktrip;
+  const bool deferred = P.shard_deferred;
+  // a weighted build takes group slots only as a SUM CSR whose codes the parse writes
+  const bool grouped = P.grouped && (!P.has_wt || P.codes_in_parse);
   // 32 tiles per group slot; a small input takes fewer, so that the partition's first pass (one block
   // per group) still has about kMinGroups blocks (C2's 3.7K tiles: 115 groups of 32 left most CUs idle)
   uint32_t gshift = kGroupShift;
@@ -1396,7 +1537,7 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
     G2N_HIP(hipMemsetAsync(gcount, 0, n_groups * sizeof(uint32_t), c->stream));
   }
   auto* tlean = dget<TileLean>(c, S_TLEAN, n_tiles);
-  ParseOpts lo{};
+  ParseOpts lo = plan_parse_opts(P);
   lo.rows = rows_p;
   lo.cols = cols_p;
   lo.ktrip = ktrip;
@@ -1408,64 +1549,31 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
   lo.gshift = gshift;
   // a whole-file build takes the unsupported-record warning itself (k_tile_lean_check); a sharded range
   // leaves it to the general protocol
-  uint32_t* tunk = warn_ok ? dget<uint32_t>(c, S_TUNK, n_tiles) : nullptr;
+  uint32_t* tunk = !P.shard_dec ? dget<uint32_t>(c, S_TUNK, n_tiles) : nullptr;
   lo.tunk = tunk;
   double* ew_p = nullptr;
-  if (xo) {
-    lo.bidir = xo->bidir;
-    lo.keep = xo->keep;
-    lo.has_wt = xo->has_wt;
-    lo.wt_len = xo->wt_len;
-    lo.wt_pack = xo->wt_pack;
-    lo.w_last = xo->w_last;
-    if (xo->has_wt && grouped) {
-      lo.wenc = dget<uint32_t>(c, S_WENCP, slots);
-      lo.wf32 = xo->wf32;
-    } else if (xo->has_wt) {
-      lo.ew = ew_p = dget<double>(c, S_EWP, n_tiles * kTileEdgeCap);
-    }
+  if (P.has_wt && grouped) {
+    lo.wenc = dget<uint32_t>(c, S_WENCP, slots);
+    lo.wf32 = P.dt == G2N_FLOAT32 ? 1u : 0u;
+  } else if (P.has_wt) {
+    lo.ew = ew_p = dget<double>(c, S_EWP, n_tiles * kTileEdgeCap);
   }
-#ifdef G2N_K2_STAMPS
-  unsigned long long* stamps = dget<unsigned long long>(c, S_TEMP, n_tiles * kK2Stamps);
-  G2N_HIP(hipMemsetAsync(stamps, 0, n_tiles * kK2Stamps * 8, c->stream));
-  G2N_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g2n_k2_stamps), &stamps, sizeof(stamps), 0, hipMemcpyHostToDevice,
-                                 c->stream));
-#endif
-  if (xo && grouped)
-    hipLaunchKernelGGL((k_tile_lean<kLeanDecimal, true, true>), dim3((unsigned)n_tiles), dim3(kLeanTPB), 0,
-                       c->stream, in, len, lo, c->ctl, tcnt, tlean, gcount, gcap, HashLeanArgs{});
-  else if (xo)
-    hipLaunchKernelGGL((k_tile_lean<kLeanDecimal, false, true>), dim3((unsigned)n_tiles), dim3(kLeanTPB), 0,
-                       c->stream, in, len, lo, c->ctl, tcnt, tlean, (uint32_t*)nullptr, (uint64_t)0, HashLeanArgs{});
-  else if (grouped)
-    hipLaunchKernelGGL((k_tile_lean<kLeanDecimal, true>), dim3((unsigned)n_tiles), dim3(kLeanTPB), 0, c->stream, in,
-                       len, lo, c->ctl, tcnt, tlean, gcount, gcap, HashLeanArgs{});
-  else
-    hipLaunchKernelGGL((k_tile_lean<kLeanDecimal, false>), dim3((unsigned)n_tiles), dim3(kLeanTPB), 0, c->stream, in,
-                       len, lo, c->ctl, tcnt, tlean, (uint32_t*)nullptr, (uint64_t)0, HashLeanArgs{});
+  launch_tile_lean<kLeanDecimal>(c, in, len, n_tiles, grouped, P.ext, lo, tcnt, tlean, gcount, gcap, HashLeanArgs{},
+                                 "G2N_K2_STAMPS_OUT");
   phase(c, "parse");
-#ifdef G2N_K2_STAMPS
-  stamps_to_file(c, "G2N_K2_STAMPS_OUT", stamps, n_tiles * kK2Stamps);
-#endif
   // the tile scan, the warning's line and the premise check run unconditionally behind the parse
   // (on a failed parse their results are dropped), so the host waits once for all of them
   {
-    const uint64_t n_parts = (n_tiles + kStructChunk - 1) / kStructChunk;
-    auto* part = dget<TileCnt>(c, S_TEMP, n_parts + 1);
-    hipLaunchKernelGGL(k_struct_reduce<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream,
-                       (const TileCnt*)tcnt, n_tiles, part);
-    hipLaunchKernelGGL(k_struct_scan_parts<TileCnt>, dim3(1), dim3(256), 0, c->stream, part, n_parts, part + n_parts);
-    hipLaunchKernelGGL(k_struct_scan_chunks<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream,
-                       (const TileCnt*)tcnt, n_tiles, (const TileCnt*)part, tbase);
+    const TileCnt* total = scan_tile_counts(c, tcnt, n_tiles, tbase);
     if (deferred)  // the range's offset evidence, checked by the caller across ranges
       hipLaunchKernelGGL(k_tile_lean_evidence, dim3(grid_for(n_tiles)), dim3(kTPB), 0, c->stream,
                          (const TileCnt*)tcnt, (const TileCnt*)tbase, (const TileLean*)tlean, n_tiles, c->ctl);
     else  // (the file's S count: n_seg_all, or the total the scan just wrote)
       hipLaunchKernelGGL(k_tile_lean_check, dim3(grid_for(n_tiles)), dim3(kTPB), 0, c->stream, (const TileCnt*)tcnt,
-                         (const TileCnt*)tbase, (const TileLean*)tlean, n_tiles, n_seg_all,
-                         (const TileCnt*)(part + n_parts), s_base, (const uint32_t*)tunk, c->ctl);
+                         (const TileCnt*)tbase, (const TileLean*)tlean, n_tiles, P.n_seg_all, total, P.s_base,
+                         (const uint32_t*)tunk, c->ctl);
     TileCnt tot;
-    G2N_HIP(hipMemcpyAsync(&tot, part + n_parts, sizeof(TileCnt), hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipMemcpyAsync(&tot, total, sizeof(TileCnt), hipMemcpyDeviceToHost, c->stream));
     sync_ctl(c);
     bool ok = !c->h_ctl->int_fail && c->h_ctl->err_key == ~0ull && tot.touches < 0xFFFFFFFFull &&
               tot.edges * ktrip < 0xFFFFFFFFull;
@@ -1505,16 +1613,6 @@ static bool tile_local_parse(g2n_context* c, const uint8_t* in, uint64_t len, ui
   return false;
 }
 
-// the edge passes' extended fields (bidirected keys / one integer weight tag) from X
-static void lean_ext_args(HashLeanArgs& H, const HashLeanArgs& X) {
-  H.bidir = X.bidir;
-  H.has_wt = X.has_wt;
-  H.wt_len = X.wt_len;
-  H.wt_pack = X.wt_pack;
-  H.ew = X.ew;
-  H.w_last = X.w_last;
-}
-
 // the lean hash / direct passes' tiles (k_tile_lists): claim = tiles with S or P / O lines, edge = with edge lines
 struct TileLists {
   const uint32_t* claim = nullptr;
@@ -1523,258 +1621,185 @@ struct TileLists {
   uint64_t n_edge = 0;
 };
 
-// The S-first hash dictionary on the lean front end (k_tile_lean kLeanClaim / kLeanEdges, after K1):
-// S names claimed with node id = S index, then every edge line's names found straight from its
-// staged tile and the stream-order COO written.  False (and a clean slate) when the input is not
-// S-first with unique names in the lean shapes: the classic parse + dictionary tiers run instead.
-static bool hash_lean_build(g2n_context* c, const uint8_t* in, uint64_t len, const TileLists& TL, const TileCnt* tcnt,
-                            const TileCnt* tbase, uint64_t n_s, uint32_t ktrip, int32_t* rows, int32_t* cols,
-                            const HashLeanArgs& X, uint64_t** noff_out, uint32_t** nlen_out, uint64_t* names_len) {
-#ifdef G2N_K2_STAMPS
-  const uint64_t n_tiles = (len + kTile - 1) / kTile;  // (the stamps buffer)
-#endif
+// The rung of the front end that produced the build's coordinates (front_end tries them in this order)
+enum class Tier {
+  kTileLocal,  // the one-pass decimal parse (plain or behind a prefix), no K1: stream-order COO or group slots
+  kDirect,     // K1, then the direct-address claim / edge passes: stream-order COO
+  kLeanHash,   // K1, then the S-first hash claim / edge passes: stream-order COO
+  kLeanParse,  // K1, then the lean decimal parse (k_tile_parse writing rows / cols)
+  kFull,       // K1, then the full parse: touches for the dictionary, coordinates by k_triplets after it
+};
+
+// what the front end did and left for the later stages
+struct FrontEnd {
+  Tier tier = Tier::kFull;
+  TileCnt tot{};
+  bool in_groups = false;      // kTileLocal: the COO is in group slots (c->gcoo), rows / cols only for a rebuild
+  bool codes = false;          // ... and the parse wrote the weights as exact-int32 codes beside it (no E.w)
+  bool tid_ok = false;         // kFull: the parse's per-touch decimal ids hold (the dictionary starts from them)
+  uint64_t dpre = 0;           // kTileLocal behind a prefix P: node k's name is P + str(k + 1)
+  uint32_t name_pre_len = 0;
+  uint64_t* noff = nullptr;    // kDirect / kLeanHash: S line k's name (node k's), and the names' bytes
+  uint32_t* nlen = nullptr;
+  uint64_t names_len = 0;
+  uint64_t* ls = nullptr;      // line starts and kinds (kFull; a lean tier that declined leaves none)
+  uint8_t* kind = nullptr;
+  TouchOut T{};
+  EdgeOut E{};
+  int32_t* rows = nullptr;     // the stream-order COO (every tier but kFull wrote it, unless in_groups)
+  int32_t* cols = nullptr;
+  bool local() const { return tier == Tier::kTileLocal; }
+  bool claimed() const { return tier == Tier::kDirect || tier == Tier::kLeanHash; }
+  bool coords() const { return tier != Tier::kFull; }  // node k is S line k: no dictionary, no triplets
+};
+
+// the lean hash / direct passes' arguments the plan and K1 give (the tier adds its table)
+static HashLeanArgs lean_args(const BuildPlan& P, const TileCnt* tbase, const TileCnt* tcnt, int32_t* rows,
+                              int32_t* cols, double* ew) {
+  HashLeanArgs H{};
+  H.tbase = tbase;
+  H.tcnt = tcnt;
+  H.rows = rows;
+  H.cols = cols;
+  H.ktrip = P.ktrip;
+  H.bidir = P.bidir ? 1 : 0;  // (bidirected keys and / or one integer weight tag: the edge passes' extended instance)
+  H.has_wt = P.has_wt;
+  H.wt_len = P.wt_len;
+  H.wt_pack = P.wt_pack;
+  H.ew = ew;
+  H.w_last = P.last ? 1u : 0u;
+  return H;
+}
+
+// A dictionary tier on the lean front end (after K1): a claim pass over the tiles with S lines, then an
+// edge pass that finds every edge line's names straight from its staged tile and writes the stream-order COO.
+// <kLeanClaim, kLeanEdges>, the S-first hash: S names claimed in a table of load <= 2/3 with node id = S index.
+// <kLeanDirClaim, kLeanDirEdges>, the direct-address tier: S names that are one prefix + a decimal v < cap (+ one
+// suffix: np) claim direct[v] = S index, and an edge name costs one 4-byte read.  cap = 4 x the S lines (at least
+// 64 Ki, at most 2^28 values: 1 GiB): ids "1".."N" out of order, or with gaps, fit.
+// False (and a clean slate) when the input is not S-first with unique names in the lean shapes — direct: when
+// any name breaks the shape, a value repeats or passes cap —: the next tier runs instead.
+template <int kClaim, int kEdges>
+static bool lean_tier_build(g2n_context* c, const uint8_t* in, uint64_t len, const TileLists& TL, uint64_t n_s,
+                            HashLeanArgs H, const NamePattern* np, FrontEnd* F) {
+  constexpr bool kDirect = kClaim == kLeanDirClaim;
   if (n_s == 0 || n_s >= 0x7FFFFFFFull) return false;
-  uint64_t cap = 1024;
-  while (cap * 67 < n_s * 100) cap <<= 1;  // load <= 2/3: probe sequences stay short
-  auto* table = dget<DictEntry>(c, S_TABLE, cap);
-  G2N_HIP(hipMemsetAsync(table, 0xFF, cap * sizeof(DictEntry), c->stream));
-  auto* noff = dget<uint64_t>(c, S_NOFF, n_s);
-  auto* nlen = dget<uint32_t>(c, S_NLEN, n_s);
-  HashLeanArgs H{tbase, tcnt, table, cap - 1, cap, noff, nlen, rows, cols, ktrip};
-  lean_ext_args(H, X);
+  uint64_t cap;
+  if constexpr (kDirect) {
+    cap = std::min<uint64_t>(1ull << 28, std::max<uint64_t>(4 * n_s, 1ull << 16));
+    H.direct = dget<uint32_t>(c, S_DIRECT, cap);
+    G2N_HIP(hipMemsetAsync(H.direct, 0xFF, cap * sizeof(uint32_t), c->stream));
+    H.direct_cap = cap;
+    H.pre = np->pre;
+    H.pre_len = np->pre_len;
+    H.suf = np->suf;
+    H.suf_len = np->suf_len;
+    H.width = np->width;
+  } else {
+    cap = 1024;
+    while (cap * 67 < n_s * 100) cap <<= 1;  // load <= 2/3: probe sequences stay short
+    H.table = dget<DictEntry>(c, S_TABLE, cap);
+    G2N_HIP(hipMemsetAsync(H.table, 0xFF, cap * sizeof(DictEntry), c->stream));
+    H.mask = cap - 1;
+    H.max_probes = cap;
+  }
+  H.noff = dget<uint64_t>(c, S_NOFF, n_s);
+  H.nlen = dget<uint32_t>(c, S_NLEN, n_s);
   phase(c, "table_init");
-#ifdef G2N_K2_STAMPS  // every k_tile_lean launch stamps: the buffer must be this build's
-  unsigned long long* stamps = dget<unsigned long long>(c, S_TEMP, n_tiles * kK2Stamps);
-  G2N_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g2n_k2_stamps), &stamps, sizeof(stamps), 0, hipMemcpyHostToDevice,
-                                 c->stream));
-#endif
   H.tlist = TL.claim;
   H.tnb = dget<unsigned long long>(c, S_TNB, TL.n_claim);
-  hipLaunchKernelGGL((k_tile_lean<kLeanClaim, false>), dim3((unsigned)TL.n_claim), dim3(kLeanTPB), 0, c->stream, in, len,
-                     ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
+  launch_tile_lean<kClaim>(c, in, len, TL.n_claim, false, false, ParseOpts{}, nullptr, nullptr, nullptr, 0, H);
   hipLaunchKernelGGL(k_claim_totals, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)H.tnb, TL.n_claim,
                      &c->ctl->names_len, &c->ctl->dir_vmax);
-  phase(c, "insert_claim");
+  if constexpr (kDirect) {  // (cap is a multiple of 4; the count stops past the largest claimed value)
+    G2N_HIP(hipMemsetAsync(&c->ctl->n_keep, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_direct_filled, dim3((unsigned)std::min<uint64_t>(grid_for(cap / 4, 256), 2048)), dim3(256), 0,
+                       c->stream, (const uint4*)H.direct, cap / 4, (const unsigned long long*)&c->ctl->dir_vmax,
+                       &c->ctl->n_keep);
+  }
+  phase(c, kDirect ? "direct_claim" : "insert_claim");
   sync_ctl(c);
-  if (c->h_ctl->int_fail) {
+  if (c->h_ctl->int_fail || (kDirect && c->h_ctl->n_keep != n_s)) {  // (a repeated value: fewer filled)
     reset_ctl(c);
     return false;
   }
-  *names_len = c->h_ctl->names_len;  // the claimed names' bytes: the names blob needs no later sync
-#ifdef G2N_K2_STAMPS
-  G2N_HIP(hipMemsetAsync(stamps, 0, n_tiles * kK2Stamps * 8, c->stream));  // the claim pass stamped too
-#endif
+  F->names_len = c->h_ctl->names_len;  // the claimed names' bytes: the names blob needs no later sync
   H.tlist = TL.edge;
-  if (!TL.n_edge) {
-  } else if (H.bidir || H.has_wt)
-    hipLaunchKernelGGL((k_tile_lean<kLeanEdges, false, true>), dim3((unsigned)TL.n_edge), dim3(kLeanTPB), 0, c->stream, in,
-                       len, ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
-  else
-    hipLaunchKernelGGL((k_tile_lean<kLeanEdges, false>), dim3((unsigned)TL.n_edge), dim3(kLeanTPB), 0, c->stream, in, len,
-                       ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
-  phase(c, "insert_lookup");
-#ifdef G2N_K2_STAMPS
-  stamps_to_file(c, "G2N_HL_STAMPS_OUT", stamps, n_tiles * kK2Stamps);  // (the edge pass)
-#endif
+  if (TL.n_edge)
+    launch_tile_lean<kEdges>(c, in, len, TL.n_edge, false, H.bidir || H.has_wt, ParseOpts{}, nullptr, nullptr, nullptr,
+                             0, H, kDirect ? nullptr : "G2N_HL_STAMPS_OUT");
+  phase(c, kDirect ? "direct_lookup" : "insert_lookup");
   sync_ctl(c);
   if (c->h_ctl->int_fail) {
     reset_ctl(c);
     return false;
   }
-  *noff_out = noff;
-  *nlen_out = nlen;
+  F->noff = H.noff;
+  F->nlen = H.nlen;
   return true;
 }
 
-// The direct-address tier on the lean front end (k_tile_lean kLeanDirClaim / kLeanDirEdges, after K1):
-// S names that are one prefix + a canonical decimal v < cap claim direct[v] = S index, then every edge
-// line's names are found with one 4-byte read each and the stream-order COO written.  cap = 4 x the S
-// lines (at least 64 Ki, at most 2^28 values: 1 GiB): ids "1".."N" out of order, or with gaps, fit.
-// False (and a clean slate) when any name breaks the shape, a value repeats or passes cap, or the
-// input is not S-first: the lean hash tier runs next.
-static bool direct_lean_build(g2n_context* c, const uint8_t* in, uint64_t len, const TileLists& TL, const TileCnt* tcnt,
-                              const TileCnt* tbase, uint64_t n_s, uint32_t ktrip, int32_t* rows, int32_t* cols,
-                              const NamePattern& np, const HashLeanArgs& X, uint64_t** noff_out, uint32_t** nlen_out,
-                              uint64_t* names_len) {
-#ifdef G2N_K2_STAMPS
-  const uint64_t n_tiles = (len + kTile - 1) / kTile;  // (the stamps buffer)
-#endif
-  if (n_s == 0 || n_s >= 0x7FFFFFFFull) return false;
-  const uint64_t cap = std::min<uint64_t>(1ull << 28, std::max<uint64_t>(4 * n_s, 1ull << 16));
-  auto* direct = dget<uint32_t>(c, S_DIRECT, cap);
-  G2N_HIP(hipMemsetAsync(direct, 0xFF, cap * sizeof(uint32_t), c->stream));
-  auto* noff = dget<uint64_t>(c, S_NOFF, n_s);
-  auto* nlen = dget<uint32_t>(c, S_NLEN, n_s);
-  HashLeanArgs H{tbase, tcnt, nullptr, 0, 0, noff, nlen, rows, cols, ktrip};
-  H.direct = direct;
-  H.direct_cap = cap;
-  H.pre = np.pre;
-  H.pre_len = np.pre_len;
-  H.suf = np.suf;
-  H.suf_len = np.suf_len;
-  H.width = np.width;
-  lean_ext_args(H, X);
-  phase(c, "table_init");
-#ifdef G2N_K2_STAMPS  // every k_tile_lean launch stamps: the buffer must be this build's
-  unsigned long long* stamps = dget<unsigned long long>(c, S_TEMP, n_tiles * kK2Stamps);
-  G2N_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g2n_k2_stamps), &stamps, sizeof(stamps), 0, hipMemcpyHostToDevice,
-                                 c->stream));
-#endif
-  H.tlist = TL.claim;
-  H.tnb = dget<unsigned long long>(c, S_TNB, TL.n_claim);
-  hipLaunchKernelGGL((k_tile_lean<kLeanDirClaim, false>), dim3((unsigned)TL.n_claim), dim3(kLeanTPB), 0, c->stream, in,
-                     len, ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
-  hipLaunchKernelGGL(k_claim_totals, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)H.tnb, TL.n_claim,
-                     &c->ctl->names_len, &c->ctl->dir_vmax);
-  // (cap is a multiple of 4; the count stops past the largest claimed value)
-  G2N_HIP(hipMemsetAsync(&c->ctl->n_keep, 0, sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(k_direct_filled, dim3((unsigned)std::min<uint64_t>(grid_for(cap / 4, 256), 2048)), dim3(256), 0,
-                     c->stream, (const uint4*)direct, cap / 4, (const unsigned long long*)&c->ctl->dir_vmax,
-                     &c->ctl->n_keep);
-  phase(c, "direct_claim");
-  sync_ctl(c);
-  if (c->h_ctl->int_fail || c->h_ctl->n_keep != n_s) {  // (a repeated value: fewer filled)
-    reset_ctl(c);
-    return false;
-  }
-  *names_len = c->h_ctl->names_len;
-  H.tlist = TL.edge;
-  if (!TL.n_edge) {
-  } else if (H.bidir || H.has_wt)
-    hipLaunchKernelGGL((k_tile_lean<kLeanDirEdges, false, true>), dim3((unsigned)TL.n_edge), dim3(kLeanTPB), 0, c->stream,
-                       in, len, ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr,
-                       (uint64_t)0, H);
-  else
-    hipLaunchKernelGGL((k_tile_lean<kLeanDirEdges, false>), dim3((unsigned)TL.n_edge), dim3(kLeanTPB), 0, c->stream, in,
-                       len, ParseOpts{}, c->ctl, (TileCnt*)nullptr, (TileLean*)nullptr, (uint32_t*)nullptr, (uint64_t)0, H);
-  phase(c, "direct_lookup");
-  sync_ctl(c);
-  if (c->h_ctl->int_fail) {
-    reset_ctl(c);
-    return false;
-  }
-  *noff_out = noff;
-  *nlen_out = nlen;
-  return true;
-}
-
-static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, g2n_result* R) {
-  fill_defaults(R);
-  clear_call_state(c);
-  c->test_flags = o->test_flags;
-  R->input_bytes = len;
-  c->n_ev = 0;
-  G2N_HIP(hipEventRecord(c->ev[0], c->stream));
-  reset_ctl(c);
-  const bool bidir = o->bidirected != 0, keep = o->keep_directed_bidir != 0;
-  const bool gd = keep || (!bidir && o->directed != 0);  // builders.py:143
-  const bool maxsym = gd && !o->asymmetric;              // builders.py:282
-  const uint32_t tps = bidir ? 2 : 1;
-  const uint32_t tpe = (bidir && !keep) ? 4 : 2;
-  const int dt = o->dtype;
-  R->dtype = dt;
-  R->index_width = 4;
-
-  const uint64_t n_tiles = (len + kTile - 1) / kTile;
+// The front end: the input parsed by the cheapest rung whose premise holds — tile-local decimal ids (plain or
+// behind a prefix), else K1 and then the direct-address tier, the lean hash tier, the lean decimal parse, the
+// full parse — and the slow weights.  A rung that declines leaves a clean slate and the next one runs, as if it
+// had not.  Sets the counts of R; the result says which rung the coordinates came from.
+static FrontEnd front_end(g2n_context* c, const uint8_t* in, uint64_t len, const BuildPlan& P, g2n_result* R) {
+  FrontEnd F;
+  const uint64_t n_tiles = P.n_tiles;
   auto* tcnt = dget<TileCnt>(c, S_TILE_CNT, n_tiles + 1);
   auto* tbase = dget<TileCnt>(c, S_TILE_BASE, n_tiles + 1);
-  TileCnt tot{};
-  const bool shard_dec = (o->range_flags & G2N_RANGE_DECIMAL) != 0;
-  // g2n_build_decimal_range: the S lines before the range are not known yet — the one-pass parse
-  // reports the range's offset evidence instead of checking it (the caller checks across ranges)
-  const bool shard_deferred = shard_dec && (o->range_flags & G2N_RANGE_EVIDENCE) != 0;
   c->range_has_s = false;
   c->range_d = -1;
   c->range_vmax = 0;
   c->range_nseg = 0;
-  const bool first_one =
-      !shard_dec && !(c->test_flags & (kTestDictHash | kTestDictGeneral | kTestDictDirect)) &&
-      first_segment_is_one(c, in, len);
+  // the first S line names "1" (a cheap guess: a wrong one costs one extra parse) ...
+  const uint32_t dict_forced = c->test_flags & (kTestDictHash | kTestDictGeneral | kTestDictDirect);
+  const bool first_one = !P.shard_dec && !dict_forced && first_segment_is_one(c, in, len);
   // ... or "P1": the same layout behind a constant prefix P (tile-local pass only: a failed one goes to
   // the direct / hash tiers, which take any prefix)
   uint64_t dpre = 0;
   uint32_t dpre_len = 0;
-  const bool first_pre = !first_one && !shard_dec && !(c->test_flags & (kTestDictHash | kTestDictGeneral |
-                                                                        kTestDictDirect | kTestNoDecPrefix)) &&
+  const bool first_pre = !first_one && !P.shard_dec && !dict_forced && !(c->test_flags & kTestNoDecPrefix) &&
                          first_segment_prefixed(c, in, len, &dpre, &dpre_len);
   // ---- the decimal-id lean parse without K1 (tile-local positions, checked and compacted after)
-  // group slots when the COO's only reader is the unweighted bucket partition (a CSR output)
-  const bool coo_wanted = (o->output == G2N_OUT_PARSE && !maxsym) || o->output == G2N_OUT_COO;
-  // ... or a sharded decimal range whose caller takes the COO as group slots (G2N_RANGE_SLOTS: unweighted,
-  // coordinates only — its route or slice CSR needs no stream order)
-  const bool slots_out = shard_dec && (o->range_flags & G2N_RANGE_SLOTS) && !(o->weight_tag && *o->weight_tag) && !bidir &&
-                         (o->range_flags & G2N_RANGE_NO_VALUES);
-  // a LAST build (the graph's weighted CSR): per-edge weights in stream order, records without a numeric
-  // tag marked (kWNone) — never group slots, never codes
-  const bool last = c->last_build;
-  if (last && !(o->weight_tag && *o->weight_tag && dt == G2N_FLOAT64 && o->output == G2N_OUT_CSR && o->asymmetric &&
-                !bidir && !shard_dec))
-    throw Failure(G2N_E_ARG, "the graph's weighted CSR: a plain float64 CSR build with a weight tag");
-  const bool grouped = (!coo_wanted || slots_out) && !c->no_group && !last &&
-                       !(c->test_flags & (kTestNoBuckets | kTestNoGroup));
-  // bidirected keys / one integer weight tag: the extended tile-local instance (whole files only)
-  const size_t wt_bytes = o->weight_tag ? std::strlen(o->weight_tag) : 0;
-  ParseOpts xo{};
-  xo.bidir = bidir;
-  xo.keep = keep;
-  xo.has_wt = wt_bytes > 0;
-  xo.wt_len = (uint32_t)wt_bytes;
-  xo.w_last = last ? 1u : 0u;
-  for (size_t k = 0; k < wt_bytes && k < 8; k++) xo.wt_pack |= (uint64_t)(uint8_t)o->weight_tag[k] << (8 * k);
-  const bool ext = bidir || wt_bytes > 0;
-  // a weighted SUM CSR in dtypes whose cast of a canonical <= 9-digit integer can neither fail nor lose
-  // the integer's exact-int32 code (float32: the code of the rounded value) takes group slots: the parse
-  // writes the codes, so neither k_tile_compact nor k_values runs (C3); a bucket partition that declines
-  // (an overfull bucket, an inexact float sum) redoes the build without groups
-  if (wt_bytes && grouped && !maxsym && o->output == G2N_OUT_CSR &&
-      (dt == G2N_FLOAT64 || dt == G2N_FLOAT32 || dt == G2N_INT32)) {
-    xo.wenc = reinterpret_cast<uint32_t*>(uintptr_t{1});  // (a flag here: tile_local_parse allocates them)
-    xo.wf32 = dt == G2N_FLOAT32 ? 1u : 0u;
-  }
-  const bool ext_ok = !shard_dec && wt_bytes <= 8 && !(c->test_flags & kTestNoExtLean);
   // (a sharded range with global decimal ids takes it too — with or without S lines of its own)
-  const bool local_done =
-      n_tiles && (first_one || first_pre ||
-                  (shard_dec && (shard_deferred || (o->range_s_base >= 0 && o->range_n_segments > 0)))) &&
-      (!ext || ext_ok) && !o->strip_orientation && !(c->test_flags & (kTestNoLean | kTestNoTileLocal)) &&
-      tile_local_parse(c, in, len, n_tiles, tpe == 4 ? 4u : (gd ? 1u : 2u), tcnt, tbase, &tot, grouped,
-                       shard_dec ? (uint64_t)o->range_s_base : 0, shard_dec ? (uint64_t)o->range_n_segments : 0,
-                       shard_deferred, ext ? &xo : nullptr, !shard_dec, dpre, first_pre ? dpre_len : 0u);
-  const uint32_t name_pre_len = local_done && first_pre ? dpre_len : 0u;  // node k's name: P + str(k + 1)
-  if (shard_deferred && n_tiles && !local_done)  // the caller counts the ranges and builds with K1 instead
+  if (n_tiles && (first_one || first_pre || (P.shard_dec && (P.shard_deferred || P.n_seg_all > 0))) &&
+      (!P.ext || P.ext_ok) && !P.strip && !(c->test_flags & (kTestNoLean | kTestNoTileLocal)) &&
+      tile_local_parse(c, in, len, P, tcnt, tbase, &F.tot, dpre, first_pre ? dpre_len : 0u)) {
+    F.tier = Tier::kTileLocal;
+    F.in_groups = c->gcoo.active;
+    F.codes = c->gcoo.active && c->gcoo.wenc;
+    F.dpre = dpre;
+    F.name_pre_len = first_pre ? dpre_len : 0u;
+  }
+  const bool local_done = F.local();
+  if (P.shard_deferred && n_tiles && !local_done)  // the caller counts the ranges and builds with K1 instead
     throw Failure(G2N_E_UNSUPPORTED, "sharded decimal-id range: the one-pass parse declined");
   // ---- K1: per-tile counts -> tile bases (and the lean hash / direct passes' tile lists: names that
   // are not the decimal ids)
   TileLists TL;
-  const bool lists_wanted = !first_one && !shard_dec;
   if (n_tiles && !local_done) {
-    hipLaunchKernelGGL(k_tile_count_r, dim3((unsigned)n_tiles), dim3(kK1TPB), 0, c->stream, in, len, tps, tpe, tcnt);
-    const uint64_t n_parts = (n_tiles + kStructChunk - 1) / kStructChunk;
-    auto* part = dget<TileCnt>(c, S_TEMP, n_parts + 1);  // chunk sums, then the total
-    hipLaunchKernelGGL(k_struct_reduce<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream,
-                       (const TileCnt*)tcnt, n_tiles, part);
-    hipLaunchKernelGGL(k_struct_scan_parts<TileCnt>, dim3(1), dim3(256), 0, c->stream, part, n_parts, part + n_parts);
-    hipLaunchKernelGGL(k_struct_scan_chunks<TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, c->stream,
-                       (const TileCnt*)tcnt, n_tiles, (const TileCnt*)part, tbase);
-    if (lists_wanted) {  // (read with the total: no second wait)
+    hipLaunchKernelGGL(k_tile_count_r, dim3((unsigned)n_tiles), dim3(kK1TPB), 0, c->stream, in, len, P.tps, P.tpe, tcnt);
+    const TileCnt* total = scan_tile_counts(c, tcnt, n_tiles, tbase);
+    if (!first_one && !P.shard_dec) {  // (read with the total: no second wait)
       auto* lists = dget<uint32_t>(c, S_TLIST, 2 + 2 * n_tiles);
       G2N_HIP(hipMemsetAsync(lists, 0, 2 * sizeof(uint32_t), c->stream));
       hipLaunchKernelGGL(k_tile_lists, dim3(grid_for(n_tiles)), dim3(kTPB), 0, c->stream, (const TileCnt*)tcnt, n_tiles,
                          lists);
       uint32_t n2[2];
       G2N_HIP(hipMemcpyAsync(n2, lists, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
-      tot = read_dev(c, part + n_parts);
+      F.tot = read_dev(c, total);
       TL = TileLists{lists + 2, n2[0], lists + 2 + n_tiles, n2[1]};
     } else {
-      tot = read_dev(c, part + n_parts);
+      F.tot = read_dev(c, total);
     }
   }
-  const uint64_t n_lines = tot.lines;
-  const uint64_t n_e = tot.edges, n_s = tot.segs;
-  const uint64_t n_t = n_s * tps + n_e * tpe;
+  const uint64_t n_lines = F.tot.lines;
+  const uint64_t n_e = F.tot.edges, n_s = F.tot.segs;
+  const uint64_t n_t = n_s * P.tps + n_e * P.tpe;
   R->n_lines = (int64_t)n_lines;
   R->n_edges = (int64_t)n_e;
-  R->n_records = (int64_t)tot.recs;
+  R->n_records = (int64_t)F.tot.recs;
   c->last_n_segs = n_s;
   if (n_t >= 0xFFFFFFFFull || n_e >= 0xFFFFFFFFull)
     throw Failure(G2N_E_UNSUPPORTED, "more than 2^32-1 node touches in one build");
@@ -1785,50 +1810,35 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   // per-edge buffers is read, so none is allocated (C5-size inputs: ~100 GB of HBM).  z(n): a buffer
   // size that is 1 for such a build.
   auto z = [&](uint64_t n) -> uint64_t { return local_done ? 1 : n; };
-  auto* ls = dget<uint64_t>(c, S_LS, z(n_lines + 1));
-  auto* kind = dget<uint8_t>(c, S_KIND, z(n_lines));
-  ParseOpts op{};
-  op.bidir = bidir;
-  op.keep = keep;
-  op.strip = o->strip_orientation != 0;
-  const size_t wtl = o->weight_tag ? std::strlen(o->weight_tag) : 0;
-  op.has_wt = wtl > 0;
-  op.wt_len = (uint32_t)wtl;
-  op.w_last = xo.w_last;
-  if (wtl && !local_done) {  // (the full parse's copy; a tile-local build compared the tag in place: a pageable
-    auto* wt = dget<uint8_t>(c, S_WT, wtl);  // H2D copy is a host wait)
-    G2N_HIP(hipMemcpyAsync(wt, o->weight_tag, wtl, hipMemcpyHostToDevice, c->stream));
+  auto* ls = F.ls = dget<uint64_t>(c, S_LS, z(n_lines + 1));
+  auto* kind = F.kind = dget<uint8_t>(c, S_KIND, z(n_lines));
+  ParseOpts op = plan_parse_opts(P);
+  if (P.has_wt && !local_done) {  // (the full parse's copy; a tile-local build compared the tag in place: a pageable
+    auto* wt = dget<uint8_t>(c, S_WT, P.wt_len);  // H2D copy is a host wait)
+    G2N_HIP(hipMemcpyAsync(wt, P.weight_tag, P.wt_len, hipMemcpyHostToDevice, c->stream));
     op.wt = wt;
   }
-  TouchOut T{dget<uint64_t>(c, S_NOFF, z(n_t)), dget<uint32_t>(c, S_NLEN, z(n_t)),
-             bidir ? dget<uint64_t>(c, S_OOFF, z(n_t)) : nullptr, bidir ? dget<uint32_t>(c, S_OLEN, z(n_t)) : nullptr,
-             dget<uint8_t>(c, S_TKIND, z(n_t))};
+  const TouchOut T = F.T =
+      TouchOut{dget<uint64_t>(c, S_NOFF, z(n_t)), dget<uint32_t>(c, S_NLEN, z(n_t)),
+               P.bidir ? dget<uint64_t>(c, S_OOFF, z(n_t)) : nullptr, P.bidir ? dget<uint32_t>(c, S_OLEN, z(n_t)) : nullptr,
+               dget<uint8_t>(c, S_TKIND, z(n_t))};
   // (E.w is read by k_values only for weights: a tile-local build holds them there when it has a tag)
   // (a grouped weighted build wrote exact-int32 codes instead: no per-edge weights at all)
-  const bool codes_done = local_done && c->gcoo.active && c->gcoo.wenc;
-  EdgeOut E{dget<double>(c, S_EW, local_done && (!wt_bytes || codes_done) ? 1 : n_e), dget<uint32_t>(c, S_ETB, z(n_e))};
-  const int ktrip = tpe == 4 ? 4 : (gd ? 1 : 2);
-  const uint64_t n_trip = n_e * (uint64_t)ktrip;
+  const EdgeOut E = F.E = EdgeOut{dget<double>(c, S_EW, local_done && (!P.has_wt || F.codes) ? 1 : n_e),
+                                  dget<uint32_t>(c, S_ETB, z(n_e))};
+  const uint64_t n_trip = n_e * (uint64_t)P.ktrip;
   // the stream-order COO holds int32 node ids (< 2^31 - 1, checked below) at 64-bit positions; the
   // partition counts its elements in 32 bits (more than 2^31 - 1 entries: int64 CSR indices, F2)
   if (n_trip >= 0xFFFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "more than 2^32-1 matrix entries");
-  // the group slots hold a grouped tile-local build's COO (GroupedCoo): rows / cols only for a rebuild
-  const bool in_groups = local_done && c->gcoo.active;
-  auto* rows = dget<int32_t>(c, S_ROWS, in_groups ? 1 : n_trip);
-  auto* cols = dget<int32_t>(c, S_COLS, in_groups ? 1 : n_trip);
-  // decimal-id dictionary, computed by the parse itself (lean: straight into rows / cols) when
-  // the first S line names "1" (a cheap guess: a wrong one costs one extra parse)
-  // options.range_flags G2N_RANGE_DECIMAL: one byte range of a sharded build whose node ids are decimal and
-  // GLOBAL: range_s_base S lines precede the range, range_n_segments S lines in the whole file (the
-  // caller checked across ranges that no edge line precedes an S line).  Lean parse or nothing.
-  if (shard_dec && (o->output != G2N_OUT_COO || o->want_node_names || o->range_s_base < 0 || o->range_n_segments < 0))
-    throw Failure(G2N_E_ARG, "sharded decimal-id build: output COO without names, s_base / n_seg >= 0");
-  const bool int_ids = n_t && (shard_dec || first_one);
-  const bool lean = int_ids && (shard_dec || !(c->test_flags & kTestNoLean));
+  auto* rows = F.rows = dget<int32_t>(c, S_ROWS, F.in_groups ? 1 : n_trip);
+  auto* cols = F.cols = dget<int32_t>(c, S_COLS, F.in_groups ? 1 : n_trip);
+  // decimal-id dictionary, computed by the parse itself (lean: straight into rows / cols)
+  const bool int_ids = n_t && (P.shard_dec || first_one);
+  const bool lean = int_ids && (P.shard_dec || !(c->test_flags & kTestNoLean));
   if (int_ids) {
     op.tid = dget<uint32_t>(c, S_TID, z(n_t));
-    op.n_seg = shard_dec ? (uint64_t)o->range_n_segments : n_s;
-    op.s_base = shard_dec ? (uint64_t)o->range_s_base : 0;
+    op.n_seg = P.shard_dec ? P.n_seg_all : n_s;
+    op.s_base = P.s_base;
   }
   auto* wl = dget<uint64_t>(c, S_WL, z(2 * n_e));
   auto* deferred = dget<DeferredLine>(c, S_DEFER, n_tiles + 1);
@@ -1836,7 +1846,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   phase(c, "_prep");
   auto parse = [&](const ParseOpts& po) {
     if (n_tiles)
-      hipLaunchKernelGGL(k_tile_parse, dim3((unsigned)n_tiles), dim3(kTPB), 0, c->stream, in, len, tbase, tps, tpe,
+      hipLaunchKernelGGL(k_tile_parse, dim3((unsigned)n_tiles), dim3(kTPB), 0, c->stream, in, len, tbase, P.tps, P.tpe,
                          po, ls, kind, T, E, c->ctl, wl, deferred, n_tiles, (TileCnt*)nullptr, (TileLean*)nullptr);
     sync_ctl(c);
     const uint64_t n_def = c->h_ctl->n_deferred;
@@ -1847,43 +1857,32 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
     phase(c, "parse");
     sync_ctl(c);
   };
-  // names that are not the decimal ids: the S-first hash dictionary on the lean front end first
-  uint64_t* hl_noff = nullptr;
-  uint32_t* hl_nlen = nullptr;
-  uint64_t hl_names_len = 0;
-  // (bidirected keys and / or one integer weight tag: the edge passes' extended instance)
-  const bool lean_hash_ok = n_tiles && !local_done && !int_ids && (!op.has_wt || wtl <= 8) && !op.strip &&
-                            !shard_dec && !(c->test_flags & (kTestDictGeneral | kTestNoHashLean)) && n_s && TL.claim;
-  HashLeanArgs X{};
-  X.bidir = bidir ? 1 : 0;
-  X.has_wt = op.has_wt;
-  X.wt_len = (uint32_t)wtl;
-  X.wt_pack = xo.wt_pack;
-  X.ew = E.w;
-  X.w_last = xo.w_last;
-  // decimal names out of S order (or behind one prefix): the direct-address tier first
-  NamePattern np;
-  const bool direct_done = lean_hash_ok && !(c->test_flags & (kTestDictHash | kTestNoDirect)) &&
-                           first_segment_pattern(c, in, len, &np) &&
-                           direct_lean_build(c, in, len, TL, tcnt, tbase, n_s, (uint32_t)ktrip, rows, cols, np,
-                                             X, &hl_noff, &hl_nlen, &hl_names_len);
-  const bool hash_done = direct_done || (lean_hash_ok && hash_lean_build(c, in, len, TL, tcnt, tbase, n_s,
-                                                                          (uint32_t)ktrip, rows, cols, X, &hl_noff,
-                                                                          &hl_nlen, &hl_names_len));
-  bool lean_done = local_done || hash_done;  // rows / cols hold the stream-order COO already
+  // ---- names that are not the decimal ids: the dictionary tiers on the lean front end first — decimal names
+  // out of S order (or behind one prefix) through the direct-address tier, else the S-first hash
+  if (n_tiles && !local_done && !int_ids && (!P.has_wt || P.wt_len <= 8) && !P.strip && !P.shard_dec &&
+      !(c->test_flags & (kTestDictGeneral | kTestNoHashLean)) && n_s && TL.claim) {
+    const HashLeanArgs H = lean_args(P, tbase, tcnt, rows, cols, E.w);
+    NamePattern np;
+    if (!(c->test_flags & (kTestDictHash | kTestNoDirect)) && first_segment_pattern(c, in, len, &np) &&
+        lean_tier_build<kLeanDirClaim, kLeanDirEdges>(c, in, len, TL, n_s, H, &np, &F))
+      F.tier = Tier::kDirect;
+    else if (lean_tier_build<kLeanClaim, kLeanEdges>(c, in, len, TL, n_s, H, nullptr, &F))
+      F.tier = Tier::kLeanHash;
+  }
+  // ---- decimal ids after K1: the lean parse writes rows / cols itself
   if (lean && !local_done) {
     ParseOpts lo = op;
     lo.rows = rows;
     lo.cols = cols;
-    lo.ktrip = (uint32_t)ktrip;
+    lo.ktrip = P.ktrip;
     parse(lo);
     // the lean parse wrote no line starts / kinds: errors, the unsupported-record warning and
     // slow weights need a full parse (decimal ids kept unless they failed)
-    lean_done = !c->h_ctl->int_fail && c->h_ctl->err_key == ~0ull && c->h_ctl->warn_line == ~0ull &&
-                c->h_ctl->wl_count == 0;
-    if (!lean_done && shard_dec)  // errors, warnings, slow weights or ids that are not decimal
-      throw Failure(G2N_E_UNSUPPORTED, "sharded decimal-id build: this range needs the general protocol");
-    if (!lean_done) {
+    if (!c->h_ctl->int_fail && c->h_ctl->err_key == ~0ull && c->h_ctl->warn_line == ~0ull && c->h_ctl->wl_count == 0) {
+      F.tier = Tier::kLeanParse;
+    } else {
+      if (P.shard_dec)  // errors, warnings, slow weights or ids that are not decimal
+        throw Failure(G2N_E_UNSUPPORTED, "sharded decimal-id build: this range needs the general protocol");
       const bool int_ok = !c->h_ctl->int_fail;
       c->h_ctl->wl_count = c->h_ctl->n_deferred = c->h_ctl->int_fail = 0;
       G2N_HIP(hipMemcpyAsync(&c->ctl->wl_count, &c->h_ctl->wl_count, sizeof(unsigned long long),
@@ -1895,7 +1894,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
       if (!int_ok) op.tid = nullptr;  // not decimal ids after all: the hash dictionary
     }
   }
-  if (!lean_done) parse(op);
+  if (F.tier == Tier::kFull) parse(op);
   const uint64_t n_work = c->h_ctl->wl_count;
   if (n_work) {
     hipLaunchKernelGGL(k_weights_slow, dim3(grid_for(n_work, 64)), dim3(64), 0, c->stream, in, len, ls, wl, n_work, op, E,
@@ -1903,9 +1902,15 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
     sync_ctl(c);
     phase(c, "weights_slow");
   }
+  F.tid_ok = op.tid && !c->h_ctl->int_fail;
+  return F;
+}
 
-  // ---- first error in stream order; the one-shot unsupported-record warning
-  uint64_t err_key = c->h_ctl->err_key;
+// The first error in stream order and the one-shot unsupported-record warning.  True: the build ends here
+// (R->status and the error's fields set).
+static bool first_error(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, const FrontEnd& F,
+                        g2n_result* R) {
+  const uint64_t err_key = c->h_ctl->err_key;
   uint64_t err_line = err_key == ~0ull ? ~0ull : (err_key >> 5);
   int err_code = err_key == ~0ull ? 0 : (int)(err_key & 31);
   // options.unknown_warned: an earlier shard of a sharded build already met an unsupported
@@ -1914,7 +1919,7 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
   if (warn_line != ~0ull) R->warn_line = (int64_t)warn_line;  // first unsupported line, warned or not
   if (warn_line != ~0ull && warn_line < err_line) {
     // (a tile-local lean build has no line starts: k_tile_lean_check found the record's offset)
-    uint64_t off = local_done ? c->h_ctl->warn_off : read_dev(c, ls + warn_line);
+    uint64_t off = F.local() ? c->h_ctl->warn_off : read_dev(c, F.ls + warn_line);
     uint8_t b = read_dev(c, in + off);
     if (b >= 0x80) {  // parser.py:127 line[:1].decode() raises
       err_line = warn_line;
@@ -1927,207 +1932,219 @@ static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_
       R->warn_line = (int64_t)warn_line;
     }
   }
-  if (err_code) {
-    R->status = err_code;
-    R->err_line = (int64_t)err_line;
-    c->err_line_off = read_dev(c, ls + err_line);
-    if (err_code == G2N_E_UNICODE && err_line != warn_line) {
-      hipLaunchKernelGGL(k_error_detail, dim3(1), dim3(1), 0, c->stream, in, len, ls, err_line, c->ctl);
-      sync_ctl(c);
-    }
-    if (err_code == G2N_E_UNICODE) {
-      R->err_detail = in + c->h_ctl->detail_off;  // device pointer
-      R->err_detail_len = (int64_t)c->h_ctl->detail_len;
-    }
-    hipLaunchKernelGGL(k_count_records, dim3(grid_for(err_line)), dim3(kTPB), 0, c->stream, kind, err_line, c->ctl);
-    R->n_records_before_error = (int64_t)read_dev(c, &c->ctl->n_records_before);
-    finish_timings(c, R);
-    return R->status;
+  if (!err_code) {
+    R->n_records_before_error = R->n_records;
+    return false;
   }
-  R->n_records_before_error = R->n_records;
+  R->status = err_code;
+  R->err_line = (int64_t)err_line;
+  c->err_line_off = read_dev(c, F.ls + err_line);
+  if (err_code == G2N_E_UNICODE && err_line != warn_line) {
+    hipLaunchKernelGGL(k_error_detail, dim3(1), dim3(1), 0, c->stream, in, len, F.ls, err_line, c->ctl);
+    sync_ctl(c);
+  }
+  if (err_code == G2N_E_UNICODE) {
+    R->err_detail = in + c->h_ctl->detail_off;  // device pointer
+    R->err_detail_len = (int64_t)c->h_ctl->detail_len;
+  }
+  hipLaunchKernelGGL(k_count_records, dim3(grid_for(err_line)), dim3(kTPB), 0, c->stream, F.kind, err_line, c->ctl);
+  R->n_records_before_error = (int64_t)read_dev(c, &c->ctl->n_records_before);
+  return true;
+}
 
-  // ---- dictionary: first-touch node ids (K4).  A lean build whose premise held has them all: node
-  // k is S line k, its key str(k + 1) (names by arithmetic, k_names_dec)
-  const bool coords_done = lean_done;  // the parse wrote rows / cols
+static void set_names(g2n_context* c, g2n_result* R, uint64_t names_len, uint8_t* blob, int64_t* offs) {
+  R->names_bytes = names_len;
+  R->names_blob = blob;
+  R->names_offsets = offs;
+  phase(c, "names");
+}
+
+// The dictionary — first-touch node ids (K4) — and the names blob.  A build whose coordinates the front end
+// wrote has the ids already: node k is S line k (decimal ids: its key str(k + 1), names by arithmetic).
+struct NodeIds {
   DictOut D{};
-  if (lean_done)
-    D.n_nodes = n_s * tps;
+  uint64_t n_nodes = 0;
+};
+static NodeIds ids_and_names(g2n_context* c, const uint8_t* in, uint64_t len, const BuildPlan& P, const FrontEnd& F,
+                             g2n_result* R) {
+  NodeIds N;
+  const uint64_t n_s = F.tot.segs, n_e = F.tot.edges;
+  const uint64_t n_st = n_s * P.tps, n_et = n_e * P.tpe;
+  if (F.coords())
+    N.D.n_nodes = n_st;
   else
     // expected distinct keys: the S keys plus a few edge-only ones — or, when S keys are under 1/32 of
     // the edge touches (an S-less range of a chunked build, an edge-list-like GFA), half the edge
     // touches: a table sized for the S keys alone overflows its probe bound and is redone at full size
-    D = build_dictionary(c, in, len, T, n_t, n_s * tps,
-                         n_s * tps + (n_s * tps * 32 < n_e * tpe ? (n_e * tpe) / 2 : (n_e * tpe) / 16) + 1024, bidir,
-                         op.tid && !c->h_ctl->int_fail ? kIntDone : kIntFailed);
-  TouchIn TI{T.noff, T.nlen, T.ooff, T.olen};
-  const uint64_t n_nodes = shard_dec ? (uint64_t)o->range_n_segments : D.n_nodes;  // global ids: the file's nodes
+    N.D = build_dictionary(c, in, len, F.T, n_st + n_et, n_st, n_st + (n_st * 32 < n_et ? n_et / 2 : n_et / 16) + 1024,
+                           P.bidir, F.tid_ok ? kIntDone : kIntFailed);
+  const DictOut& D = N.D;
+  const uint64_t n_nodes = N.n_nodes = P.shard_dec ? P.n_seg_all : D.n_nodes;  // global ids: the file's nodes
   if (n_nodes >= 0x7FFFFFFFull) throw Failure(G2N_E_UNSUPPORTED, "more than 2^31-1 nodes");
   R->n_nodes = (int64_t)n_nodes;
   phase(c, "ids");
-  const bool throw_after_ids = (c->test_flags & kTestThrowAfterIds) != 0;
-  if (o->want_node_names && hash_done && bidir) {  // nodes 2k / 2k + 1: S line k's name + ":+" / ":-"
+  if (!P.names) {
+  } else if (F.claimed() && P.bidir) {  // nodes 2k / 2k + 1: S line k's name + ":+" / ":-"
     auto* offs = dget<int64_t>(c, S_OFFS, n_nodes + 1);
     auto* soff = dget<int64_t>(c, S_TEMP, n_s + 1);
-    scan_excl<uint32_t, int64_t>(c, hl_nlen, soff, n_s, soff + n_s);
-    const uint64_t names_len = 2 * hl_names_len + 4 * n_s;
+    scan_excl<uint32_t, int64_t>(c, F.nlen, soff, n_s, soff + n_s);
+    const uint64_t names_len = 2 * F.names_len + 4 * n_s;
     auto* blob = dget<uint8_t>(c, S_BLOB, names_len);
     hipLaunchKernelGGL(k_names_lean_bidir, dim3(grid_for(n_s + 1)), dim3(kTPB), 0, c->stream, in,
-                       (const uint64_t*)hl_noff, (const uint32_t*)hl_nlen, (const int64_t*)soff, n_s, offs, blob);
-    R->names_bytes = names_len;
-    R->names_blob = blob;
-    R->names_offsets = offs;
-    phase(c, "names");
-  } else if (o->want_node_names && hash_done) {  // node k's name: S line k's (noff / nlen from the claims)
+                       (const uint64_t*)F.noff, (const uint32_t*)F.nlen, (const int64_t*)soff, n_s, offs, blob);
+    set_names(c, R, names_len, blob, offs);
+  } else if (F.claimed()) {  // node k's name: S line k's (noff / nlen from the claims)
     auto* offs = dget<int64_t>(c, S_OFFS, n_nodes + 1);
-    scan_excl<uint32_t, int64_t>(c, hl_nlen, offs, n_nodes);
-    hipLaunchKernelGGL(k_names_total, dim3(1), dim3(1), 0, c->stream, (const uint32_t*)hl_nlen, n_nodes, offs, c->ctl);
-    const uint64_t names_len = hl_names_len;
-    auto* blob = dget<uint8_t>(c, S_BLOB, names_len);
+    scan_excl<uint32_t, int64_t>(c, F.nlen, offs, n_nodes);
+    hipLaunchKernelGGL(k_names_total, dim3(1), dim3(1), 0, c->stream, (const uint32_t*)F.nlen, n_nodes, offs, c->ctl);
+    auto* blob = dget<uint8_t>(c, S_BLOB, F.names_len);
     if (n_nodes) {  // the copy on the side stream, overlapping the assembly's finish (fork_side)
-      const uint64_t* no = hl_noff;
-      const uint32_t* nl = hl_nlen;
+      const uint64_t* no = F.noff;
+      const uint32_t* nl = F.nlen;
       c->side_work = [c, in, len, no, nl, n_nodes, offs, blob]() {
         hipLaunchKernelGGL(k_names, dim3(grid_for(n_nodes)), dim3(kTPB), 0, c->side, in, len,
                            TouchIn{(uint64_t*)no, (uint32_t*)nl, nullptr, nullptr}, n_nodes, (const uint32_t*)nullptr,
                            (const int64_t*)offs, 0, blob);
       };
     }
-    R->names_bytes = names_len;
-    R->names_blob = blob;
-    R->names_offsets = offs;
-    phase(c, "names");
-  } else if (o->want_node_names && lean_done && (c->edge_text || c->stats_names) && !name_pre_len) {
+    set_names(c, R, F.names_len, blob, offs);
+  } else if (F.coords() && (c->edge_text || c->stats_names) && !F.name_pre_len) {
     c->names_dec = true;  // k_edge_dec_text renders them from the ids; the stats' ASCII check needs none
-  } else if (o->want_node_names && lean_done) {
+  } else if (F.coords()) {
     auto* offs = dget<int64_t>(c, S_OFFS, n_nodes + 1);
-    const uint64_t names_len = dec_name_off(n_nodes, (int)bidir) + (uint64_t)name_pre_len * n_nodes;
+    const uint64_t names_len = dec_name_off(n_nodes, (int)P.bidir) + (uint64_t)F.name_pre_len * n_nodes;
     auto* blob = dget<uint8_t>(c, S_BLOB, names_len);
     // no input but n_nodes: on the side stream, overlapping the assembly's finish (fork_side in
     // csr_partition; joined in finish_timings)
-    const int bd = (int)bidir;
-    const uint32_t pl = name_pre_len;
+    const int bd = (int)P.bidir;
+    const uint64_t dpre = F.dpre;
+    const uint32_t pl = F.name_pre_len;
     c->side_work = [c, n_nodes, bd, offs, blob, dpre, pl]() {
       hipLaunchKernelGGL(k_names_dec, dim3(grid_for(n_nodes + 1)), dim3(kTPB), 0, c->side, n_nodes, bd, offs, blob,
                          dpre, pl);
     };
-    R->names_bytes = names_len;
-    R->names_blob = blob;
-    R->names_offsets = offs;
-    phase(c, "names");
-  } else if (o->want_node_names) {  // names blob + offsets in id order
+    set_names(c, R, names_len, blob, offs);
+  } else {  // names blob + offsets in id order
     auto* offs = dget<int64_t>(c, S_OFFS, n_nodes + 1);
     scan_excl<uint32_t, int64_t>(c, D.klen, offs, n_nodes);
     hipLaunchKernelGGL(k_names_total, dim3(1), dim3(1), 0, c->stream, D.klen, n_nodes, offs, c->ctl);
     const uint64_t names_len = read_dev(c, &c->ctl->names_len);
     auto* blob = dget<uint8_t>(c, S_BLOB, names_len);
     if (n_nodes)
-      hipLaunchKernelGGL(k_names, dim3(grid_for(n_nodes)), dim3(kTPB), 0, c->stream, in, len, TI, n_nodes, D.inv,
-                         offs, (int)bidir, blob);
-    R->names_bytes = names_len;
-    R->names_blob = blob;
-    R->names_offsets = offs;
-    phase(c, "names");
+      hipLaunchKernelGGL(k_names, dim3(grid_for(n_nodes)), dim3(kTPB), 0, c->stream, in, len,
+                         TouchIn{F.T.noff, F.T.nlen, F.T.ooff, F.T.olen}, n_nodes, D.inv, offs, (int)P.bidir, blob);
+    set_names(c, R, names_len, blob, offs);
   }
-  if (throw_after_ids) throw Failure(G2N_E_DEVICE, "test: injected failure after the ids");
+  if (c->test_flags & kTestThrowAfterIds) throw Failure(G2N_E_DEVICE, "test: injected failure after the ids");
+  return N;
+}
 
-  // ---- triplets (K6): stream-order COO with the dtype cast
+// The values of the stream-order COO with the dtype cast — beside the coordinates the front end wrote, or with
+// them from the dictionary (K6, k_triplets) — and the cast's verdict.  Null: a cast failed (R->status set).
+static void* cast_values(g2n_context* c, const g2n_options* o, const BuildPlan& P, const FrontEnd& F, const DictOut& D,
+                         g2n_result* R) {
+  const uint64_t n_e = F.tot.edges, n_trip = n_e * (uint64_t)P.ktrip;
+  const bool uni = !P.has_wt;  // no weight tag: every entry is dtype(1.0)
   // values: not for a grouped build whose every value is dtype(1) (the partition reads none)
-  void* data = dbuf(c, S_DATA, (in_groups && (!o->weight_tag || codes_done)) ? 16 : n_trip * dtype_size(dt));
-  const bool uni = !op.has_wt;  // no weight tag: every entry is dtype(1.0)
-  const bool coo_out = (o->output == G2N_OUT_PARSE && !maxsym) || o->output == G2N_OUT_COO;
-  EdgeIn EI{E.w, E.tb};
+  void* data = dbuf(c, S_DATA, (F.in_groups && (uni || F.codes)) ? 16 : n_trip * dtype_size(P.dt));
   phase(c, "_prep");
-  // options.range_flags G2N_RANGE_NO_VALUES: a sharded range (decimal, or a general-protocol local build) whose
-  // caller routes coordinates only (uniform values, no COO result): the values array is left unwritten
-  const bool no_values = uni && (o->range_flags & G2N_RANGE_NO_VALUES) != 0;
-  if (coords_done) {  // values only, and only when the output or the sums read them
-    if (codes_done) c->wenc = c->gcoo.wenc;  // the partition sums the parse's codes; no value is cast
-    if (n_e && (coo_out || !uni) && !no_values && !codes_done) {
+  // the cast's verdict needs a host wait only when a cast ran (a build whose values are all dtype(1)
+  // and unread — C2, C4 — goes on to the assembly without one)
+  bool cast_ran = false;
+  if (F.coords()) {  // values only, and only when the output or the sums read them
+    if (F.codes) c->wenc = c->gcoo.wenc;  // the partition sums the parse's codes; no value is cast
+    if (n_e && (P.coo_out || !uni) && !P.no_values && !F.codes) {
       // a weighted SUM CSR: the exact-int32 codes the bucket partition sums (csr_partition_w) beside
       uint32_t* enc = nullptr;
-      if (!uni && !maxsym && !last && o->output == G2N_OUT_CSR && !(c->test_flags & kTestNoBuckets) &&
+      if (!uni && !P.maxsym && !P.last && o->output == G2N_OUT_CSR && !(c->test_flags & kTestNoBuckets) &&
           n_trip <= 0x7FFFFFFFull)
         c->wenc = enc = dget<uint32_t>(c, S_WENC, n_trip);
-#define G2N_VALUES(T) \
-  hipLaunchKernelGGL(k_values<T>, dim3(grid_for(n_e)), dim3(kTPB), 0, c->stream, E.w, n_e, ktrip, (int)uni, (T*)data, \
-                     c->ctl, enc)
-      switch (dt) {
-        case G2N_BOOL: G2N_VALUES(uint8_t); break;
-        case G2N_INT8: G2N_VALUES(int8_t); break;
-        case G2N_INT32: G2N_VALUES(int32_t); break;
-        case G2N_FLOAT32: G2N_VALUES(float); break;
-        default: G2N_VALUES(double); break;
-      }
-#undef G2N_VALUES
+      with_dtype(P.dt, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_values<T>, dim3(grid_for(n_e)), dim3(kTPB), 0, c->stream, F.E.w, n_e, (int)P.ktrip, (int)uni,
+                           (T*)data, c->ctl, enc);
+      });
+      cast_ran = true;
     }
     phase(c, "values");
   } else {
-    switch (dt) {
-      case G2N_BOOL: run_triplets<uint8_t>(c, EI, n_e, D.slot, D.table, D.tid, (int)tpe, gd, rows, cols, data); break;
-      case G2N_INT8: run_triplets<int8_t>(c, EI, n_e, D.slot, D.table, D.tid, (int)tpe, gd, rows, cols, data); break;
-      case G2N_INT32: run_triplets<int32_t>(c, EI, n_e, D.slot, D.table, D.tid, (int)tpe, gd, rows, cols, data); break;
-      case G2N_FLOAT32: run_triplets<float>(c, EI, n_e, D.slot, D.table, D.tid, (int)tpe, gd, rows, cols, data); break;
-      default: run_triplets<double>(c, EI, n_e, D.slot, D.table, D.tid, (int)tpe, gd, rows, cols, data); break;
-    }
+    with_dtype(P.dt, [&](auto tag) {
+      run_triplets<decltype(tag)>(c, EdgeIn{F.E.w, F.E.tb}, n_e, D.slot, D.table, D.tid, (int)P.tpe, P.gd, F.rows, F.cols,
+                                  data);
+    });
+    cast_ran = true;
     phase(c, "triplets");
   }
-  // the cast's verdict needs a host wait only when a cast ran (a build whose values are all dtype(1)
-  // and unread — C2, C4 — goes on to the assembly without one)
-  const bool cast_ran = !coords_done || (n_e && (coo_out || !uni) && !no_values && !codes_done);
-  if (cast_ran) sync_ctl(c);
-  const uint64_t cast_key = cast_ran ? c->h_ctl->cast_key : ~0ull;
-  R->n_cast_overflow = cast_ran ? (int64_t)(c->h_ctl->n_f32_overflow * (uint64_t)ktrip) : 0;
-  if (cast_key != ~0ull) {  // np.array(data, dtype) raises at the first bad element
-    R->status = (int)(cast_key & 15);
-    R->err_index = (int64_t)(cast_key >> 4);
-    R->err_value = read_dev(c, E.w + (cast_key >> 4) / ktrip);
-    finish_timings(c, R);
-    return R->status;
-  }
-  if (coo_out) {  // builders.py:281: the COO itself
+  if (!cast_ran) return data;
+  sync_ctl(c);
+  R->n_cast_overflow = (int64_t)(c->h_ctl->n_f32_overflow * (uint64_t)P.ktrip);
+  const uint64_t cast_key = c->h_ctl->cast_key;
+  if (cast_key == ~0ull) return data;
+  R->status = (int)(cast_key & 15);  // np.array(data, dtype) raises at the first bad element
+  R->err_index = (int64_t)(cast_key >> 4);
+  R->err_value = read_dev(c, F.E.w + (cast_key >> 4) / P.ktrip);
+  return nullptr;
+}
+
+// The result: the COO itself, the graph's weighted CSR (LAST), or the assembled CSR.  False: the bucket
+// partition refused the group-slot COO (an overfull bucket) — the build is redone without groups.
+static bool build_output(g2n_context* c, const BuildPlan& P, const FrontEnd& F, uint64_t n_nodes, void* data,
+                         g2n_result* R) {
+  const uint64_t n_trip = F.tot.edges * (uint64_t)P.ktrip;
+  if (P.coo_out) {  // builders.py:281: the COO itself
     R->format = G2N_FMT_COO;
     R->nnz = (int64_t)n_trip;
-    R->rows = rows;
-    R->cols = cols;
+    R->rows = F.rows;
+    R->cols = F.cols;
     R->data = data;
     c->slots = GroupedCoo{};
-    if (in_groups) {  // G2N_RANGE_SLOTS: the group slots themselves (g2n_context_group_slots)
+    if (F.in_groups) {  // G2N_RANGE_SLOTS: the group slots themselves (g2n_context_group_slots)
       c->slots = c->gcoo;
       R->rows = c->gcoo.rows;
       R->cols = c->gcoo.cols;
       c->gcoo.active = false;
     }
-    finish_timings(c, R);
-    return G2N_OK;
+    return true;
   }
-  if (last) {  // (float64, asymmetric, never grouped: checked above)
-    csr_last(c, rows, cols, (const double*)data, n_trip, n_nodes, R);
-    finish_timings(c, R);
-    return G2N_OK;
+  if (P.last) {  // (float64, asymmetric, never grouped: checked by make_plan)
+    csr_last(c, F.rows, F.cols, (const double*)data, n_trip, n_nodes, R);
+    return true;
   }
-  switch (dt) {
-    case G2N_BOOL: assemble<uint8_t>(c, rows, cols, (const uint8_t*)data, n_trip, n_nodes, n_nodes, maxsym, uni, R); break;
-    case G2N_INT8: assemble<int8_t>(c, rows, cols, (const int8_t*)data, n_trip, n_nodes, n_nodes, maxsym, uni, R); break;
-    case G2N_INT32: assemble<int32_t>(c, rows, cols, (const int32_t*)data, n_trip, n_nodes, n_nodes, maxsym, uni, R); break;
-    case G2N_FLOAT32: assemble<float>(c, rows, cols, (const float*)data, n_trip, n_nodes, n_nodes, maxsym, uni, R); break;
-    default: assemble<double>(c, rows, cols, (const double*)data, n_trip, n_nodes, n_nodes, maxsym, uni, R); break;
-  }
-  if (c->gcoo.failed) {  // the partition refused the group-slot COO (an overfull bucket): once more without
+  with_dtype(P.dt, [&](auto tag) {
+    using T = decltype(tag);
+    assemble<T>(c, F.rows, F.cols, (const T*)data, n_trip, n_nodes, n_nodes, P.maxsym, !P.has_wt, R);
+  });
+  if (c->gcoo.failed) {
     c->gcoo = GroupedCoo{};
-    c->no_group = true;
-    int rc;
-    try {
-      rc = run_build(c, in, len, o, R);
-    } catch (...) {
-      c->no_group = false;
-      throw;
-    }
-    c->no_group = false;
-    return rc;
+    return false;
   }
   c->gcoo.active = false;
-  finish_timings(c, R);
-  return G2N_OK;
+  return true;
+}
+
+// One build: plan, front end, first error and warning, ids and names, values, output — once more without
+// group slots when the bucket partition refused them.
+static int run_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, g2n_result* R) {
+  for (bool no_group = false;; no_group = true) {
+    fill_defaults(R);
+    clear_call_state(c);
+    c->test_flags = o->test_flags;
+    R->input_bytes = len;
+    c->n_ev = 0;
+    G2N_HIP(hipEventRecord(c->ev[0], c->stream));
+    reset_ctl(c);
+    const BuildPlan P = make_plan(c, o, len, no_group);
+    R->dtype = P.dt;
+    R->index_width = 4;
+    const FrontEnd F = front_end(c, in, len, P, R);
+    if (!first_error(c, in, len, o, F, R)) {
+      const NodeIds N = ids_and_names(c, in, len, P, F, R);
+      void* data = cast_values(c, o, P, F, N.D, R);
+      if (data && !build_output(c, P, F, N.n_nodes, data, R)) continue;
+    }
+    finish_timings(c, R);
+    return R->status;
+  }
 }
 
 // export --format edge-list (cli.py:264-281).  The lines come from the same parse: the
@@ -2544,17 +2561,10 @@ int coo_to_csr(const void* rows, const void* cols, const void* data, int64_t nnz
     G2N_HIP(hipMemcpyAsync(dc, cols, (size_t)nnz * 4, hipMemcpyHostToDevice, c->stream));
     G2N_HIP(hipMemcpyAsync(dd, data, (size_t)nnz * w, hipMemcpyHostToDevice, c->stream));
     const unsigned g = (unsigned)std::min<uint64_t>(grid_for((uint64_t)nnz), 8192);
-    switch (dtype) {
-      case G2N_BOOL:
-      case G2N_INT8: hipLaunchKernelGGL(k_values_not_one<uint8_t>, dim3(g), dim3(kTPB), 0, c->stream,
-                                        (const uint8_t*)dd, (uint64_t)nnz, not_one); break;
-      case G2N_INT32: hipLaunchKernelGGL(k_values_not_one<int32_t>, dim3(g), dim3(kTPB), 0, c->stream,
-                                         (const int32_t*)dd, (uint64_t)nnz, not_one); break;
-      case G2N_FLOAT32: hipLaunchKernelGGL(k_values_not_one<float>, dim3(g), dim3(kTPB), 0, c->stream,
-                                           (const float*)dd, (uint64_t)nnz, not_one); break;
-      default: hipLaunchKernelGGL(k_values_not_one<double>, dim3(g), dim3(kTPB), 0, c->stream, (const double*)dd,
-                                  (uint64_t)nnz, not_one); break;
-    }
+    with_dtype(dtype, [&](auto tag) {  // (int8 compared as bytes: one instantiation with bool)
+      using T = std::conditional_t<std::is_same_v<decltype(tag), int8_t>, uint8_t, decltype(tag)>;
+      hipLaunchKernelGGL(k_values_not_one<T>, dim3(g), dim3(kTPB), 0, c->stream, (const T*)dd, (uint64_t)nnz, not_one);
+    });
   }
   // the unweighted partition packs (col << 2 | side) in 32 bits: columns below 2^30
   const bool uniform = nnz > 0 && n_cols < (1ll << 30) && read_dev(c, not_one) == 0u;
@@ -2568,13 +2578,10 @@ int coo_to_csr(const void* rows, const void* cols, const void* data, int64_t nnz
   D.dtype = dtype;
   D.index_width = 4;
   D.n_nodes = n_rows;
-  switch (dtype) {
-    case G2N_BOOL: coo_to_csr_t<uint8_t>(c, dr, dc, (const uint8_t*)dd, nnz, n_rows, n_cols, uniform, &D, force_unsorted); break;
-    case G2N_INT8: coo_to_csr_t<int8_t>(c, dr, dc, (const int8_t*)dd, nnz, n_rows, n_cols, uniform, &D, force_unsorted); break;
-    case G2N_INT32: coo_to_csr_t<int32_t>(c, dr, dc, (const int32_t*)dd, nnz, n_rows, n_cols, uniform, &D, force_unsorted); break;
-    case G2N_FLOAT32: coo_to_csr_t<float>(c, dr, dc, (const float*)dd, nnz, n_rows, n_cols, uniform, &D, force_unsorted); break;
-    default: coo_to_csr_t<double>(c, dr, dc, (const double*)dd, nnz, n_rows, n_cols, uniform, &D, force_unsorted); break;
-  }
+  with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    coo_to_csr_t<T>(c, dr, dc, (const T*)dd, nnz, n_rows, n_cols, uniform, &D, force_unsorted);
+  });
   finish_timings(c, &D);
   HostResult* H = new_host_result();
   try {
@@ -2899,18 +2906,11 @@ void csr_from_group_slots(g2n_context* c, const GroupedCoo& g, uint64_t n_entrie
   c->gcoo = g;
   c->gcoo.active = true;
   bool ok = false;
-  auto go = [&](auto tag) {
-    using T = decltype(tag);
-    ok = csr_partition<T>(c, g.rows, g.cols, n_entries, n_rows, !maxsym, R);
-  };
   try {
-    switch (dtype) {
-      case G2N_BOOL: go(uint8_t{}); break;
-      case G2N_INT8: go(int8_t{}); break;
-      case G2N_INT32: go(int32_t{}); break;
-      case G2N_FLOAT32: go(float{}); break;
-      default: go(double{}); break;
-    }
+    with_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      ok = csr_partition<T>(c, g.rows, g.cols, n_entries, n_rows, !maxsym, R);
+    });
   } catch (...) {
     c->gcoo = GroupedCoo{};
     throw;
@@ -2931,7 +2931,7 @@ void csr_from_coo_pair(g2n_context* c, const int32_t* ar, const int32_t* ac, con
   R->dtype = dtype;
   R->index_width = 4;
   R->n_nodes = (int64_t)n_rows;
-  auto go = [&](auto tag) {
+  with_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     if (uniform)
       assemble_pair_t<T, true>(c, ar, ac, (const T*)ad, an, tr, tc, (const T*)td, tn, maxsym != 0, base, n_rows,
@@ -2939,14 +2939,7 @@ void csr_from_coo_pair(g2n_context* c, const int32_t* ar, const int32_t* ac, con
     else
       assemble_pair_t<T, false>(c, ar, ac, (const T*)ad, an, tr, tc, (const T*)td, tn, maxsym != 0, base, n_rows,
                                 force_unsorted, R);
-  };
-  switch (dtype) {
-    case G2N_BOOL: go(uint8_t{}); break;
-    case G2N_INT8: go(int8_t{}); break;
-    case G2N_INT32: go(int32_t{}); break;
-    case G2N_FLOAT32: go(float{}); break;
-    default: go(double{}); break;
-  }
+  });
   (void)n_cols;
   finish_timings(c, R);
 }
@@ -3273,15 +3266,9 @@ int g2n_count_device(g2n_context* ctx, const void* d_input, size_t len, int64_t*
     g2n::TileCnt tot{};
     if (n_tiles) {
       auto* tcnt = g2n::dget<g2n::TileCnt>(ctx, g2n::S_TILE_CNT, n_tiles + 1);
-      const uint64_t n_parts = (n_tiles + g2n::kStructChunk - 1) / g2n::kStructChunk;
-      auto* part = g2n::dget<g2n::TileCnt>(ctx, g2n::S_TEMP, n_parts + 1);
       hipLaunchKernelGGL(g2n::k_tile_count_r, dim3((unsigned)n_tiles), dim3(g2n::kK1TPB), 0, ctx->stream,
                          (const uint8_t*)d_input, (uint64_t)len, 1u, 2u, tcnt);
-      hipLaunchKernelGGL(g2n::k_struct_reduce<g2n::TileCnt>, dim3((unsigned)n_parts), dim3(256), 0, ctx->stream,
-                         (const g2n::TileCnt*)tcnt, n_tiles, part);
-      hipLaunchKernelGGL(g2n::k_struct_scan_parts<g2n::TileCnt>, dim3(1), dim3(256), 0, ctx->stream, part, n_parts,
-                         part + n_parts);
-      tot = g2n::read_dev(ctx, part + n_parts);
+      tot = g2n::read_dev(ctx, g2n::scan_tile_counts(ctx, tcnt, n_tiles, nullptr));  // (the total only)
     }
     out4[0] = (int64_t)tot.lines;
     out4[1] = (int64_t)tot.segs;

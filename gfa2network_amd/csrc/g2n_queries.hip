@@ -29,6 +29,18 @@ static void with_index_type(int32_t index_width, const void* indptr, const void*
   else f((const int64_t*)indptr, (const int64_t*)indices);
 }
 
+// f(T{}) with T the element type of a G2N dtype code (declared in g2n_pipeline.hip, whose builds call it too)
+template <class F>
+static void with_dtype(int dt, F&& f) {
+  switch (dt) {
+    case G2N_BOOL: f(uint8_t{}); break;
+    case G2N_INT8: f(int8_t{}); break;
+    case G2N_INT32: f(int32_t{}); break;
+    case G2N_FLOAT32: f(float{}); break;
+    default: f(double{}); break;
+  }
+}
+
 // A CSR's description, before anything is read; `who` is the public function the messages name.
 // ptrs_ok: the pointers the entry point needs whatever the sizes; entries_ok: those it needs when
 // there are entries; need_rows: entries without rows are refused here (a _host entry leaves that to

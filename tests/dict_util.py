@@ -229,7 +229,7 @@ def blob_of(keys) -> bytes:
 
 # ------------------------------------------------------------------ geometry restated from the host ------
 def lean_cap(n_s: int) -> int:
-    """hash_lean_build: the smallest power of two >= 1024 with cap * 67 >= n_s * 100."""
+    """lean_tier_build (the hash tier): the smallest power of two >= 1024 with cap * 67 >= n_s * 100."""
     cap = MIN_CAP
     while cap * 67 < n_s * 100:
         cap *= 2
@@ -380,7 +380,7 @@ def expected_table_inits(lines, route: str, bidirected: bool = False, keep: bool
     tier = expected_tier(lines, route, bidirected, keep)
     if tier == "either":
         return None
-    n = 1 if route == "lean" and any(_fields(x)[0] == b"S" for x in lines) else 0  # hash_lean_build's table
+    n = 1 if route == "lean" and any(_fields(x)[0] == b"S" for x in lines) else 0  # lean_tier_build's hash table
     if tier == "lean":
         return n
     n += 1 if route != "general" else 0  # the S-first attempt
