@@ -7,12 +7,12 @@ gfa2network/__init__.py:3-14).  The work runs in hand-written gfx950 kernels beh
 C-ABI in include/g2n.h (libg2n.so, loaded with ctypes).
 """
 from .api import (compute_stats, convert_format, export_edge_list, export_graph_json, genome_distance, genome_distance_matrix,
-                  graph_matrix, graph_stats, load_paths, parse_gfa, parse_gfa_sharded, path_distances, sequence_distance,
-                  sequence_nodes)
+                  graph_matrix, graph_stats, load_paths, node_distances, pair_sums, parse_gfa, parse_gfa_sharded, path_distances,
+                  sequence_distance, sequence_nodes)
 
 __version__ = "0.3.0"
 
 __all__ = ["parse_gfa", "parse_gfa_sharded", "convert_format", "export_edge_list", "export_graph_json", "compute_stats", "graph_stats",
            "graph_matrix",
-           "path_distances", "load_paths", "genome_distance", "genome_distance_matrix", "sequence_distance",
+           "path_distances", "node_distances", "pair_sums", "load_paths", "genome_distance", "genome_distance_matrix", "sequence_distance",
            "sequence_nodes", "__version__"]

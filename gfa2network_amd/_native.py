@@ -45,6 +45,8 @@ EXPORTED = [
     "g2n_distances_from_path", "g2n_csr_path_distances_weighted", "g2n_csr_path_distances_weighted_host",
     "g2n_seq_distance_from_path", "g2n_seq_hits_get", "g2n_seq_hits_names", "g2n_seq_hits_free",
     "g2n_graph_weights_from_path", "g2n_wdistances_from_path", "g2n_seq_wdistance_from_path",
+    "g2n_csr_pair_distances", "g2n_csr_pair_distances_weighted", "g2n_csr_pair_distances_host",
+    "g2n_csr_pair_distances_weighted_host", "g2n_pair_distances_from_path",
 ]
 
 
@@ -396,6 +398,22 @@ def load() -> ctypes.CDLL:
                                                 ctypes.POINTER(SeqInfo), ctypes.POINTER(I32), ctypes.POINTER(I32),
                                                 ctypes.POINTER(ctypes.POINTER(Result))]
     lib.g2n_seq_wdistance_from_path.restype = ctypes.c_int
+    lib.g2n_csr_pair_distances.argtypes = [P, P, P, I32, U64, U64, P, U64, P, U64, I32, P, ctypes.POINTER(DistInfo)]
+    lib.g2n_csr_pair_distances.restype = ctypes.c_int
+    lib.g2n_csr_pair_distances_weighted.argtypes = [P, P, P, I32, P, U64, U64, P, U64, P, U64, P,
+                                                    ctypes.POINTER(WDistInfo)]
+    lib.g2n_csr_pair_distances_weighted.restype = ctypes.c_int
+    lib.g2n_csr_pair_distances_host.argtypes = [P, P, I32, U64, U64, P, U64, P, U64, I32, P, I32,
+                                                ctypes.POINTER(DistInfo)]
+    lib.g2n_csr_pair_distances_host.restype = ctypes.c_int
+    lib.g2n_csr_pair_distances_weighted_host.argtypes = [P, P, I32, P, U64, U64, P, U64, P, U64, P, I32,
+                                                         ctypes.POINTER(WDistInfo)]
+    lib.g2n_csr_pair_distances_weighted_host.restype = ctypes.c_int
+    lib.g2n_pair_distances_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), P, I64, I64, I32, P,
+                                                 ctypes.POINTER(DistInfo), ctypes.POINTER(WDistInfo),
+                                                 ctypes.POINTER(I32), ctypes.POINTER(I64), ctypes.POINTER(I32),
+                                                 ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_pair_distances_from_path.restype = ctypes.c_int
     lib.g2n_seq_hits_get.argtypes = [P] + [P] * 4
     lib.g2n_seq_hits_get.restype = None
     lib.g2n_seq_hits_names.argtypes = [P, P, P]
@@ -671,6 +689,84 @@ def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, va
         raise RuntimeError(f"{status_name(rc)}: {last_error()}")
     tabs = (out[0], out[1].view(np.uint64)) if mean else (out[0],)
     return tabs, _wdist_info(info)
+
+
+PAIR_SUMS, PAIR_TABLE = 0, 1
+
+
+def _dist_info(info: DistInfo) -> dict:
+    return {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
+            "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
+
+
+def csr_pair_distances_host(indptr: np.ndarray, indices: np.ndarray, values, n: int, sources: np.ndarray,
+                            targets: np.ndarray, table: bool, device: int = 0) -> tuple[tuple, dict]:
+    """g2n_csr_pair_distances_host (``values`` None) / g2n_csr_pair_distances_weighted_host (float64
+    ``values``; the table only) on a host CSR (indptr / indices both int32 or both int64) and two int64
+    id lists (-1: no node): ((S, C), info) — uint64, len(sources) each — or, ``table``, ((D,), info) —
+    len(sources) x len(targets), uint32 (0xFFFFFFFF = unreached) or float64 (inf).  info: the
+    g2n_dist_info fields, or g2n_wdist_info's with values."""
+    lib = load()
+    idt = np.dtype(indptr.dtype)
+    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
+        raise TypeError("indptr / indices must both be int32 or both int64")
+    ip, ix = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
+    if len(ip) != n + 1:
+        raise ValueError("indptr must hold n + 1 offsets")
+    src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+    tgt = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+    weighted = values is not None
+    if weighted:
+        if not table:
+            raise ValueError("the weighted pair distances are a table (a float sum's order is the caller's)")
+        if np.dtype(values.dtype) != np.dtype(np.float64):
+            raise TypeError("values must be float64")
+        val = np.ascontiguousarray(values)
+        if len(val) != len(ix):
+            raise ValueError("values must hold one value per index")
+        out = np.empty((len(src), len(tgt)), dtype=np.float64)
+        info = WDistInfo()
+        rc = lib.g2n_csr_pair_distances_weighted_host(
+            ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, val.ctypes.data if val.size else None, n,
+            len(ix), src.ctypes.data if src.size else None, len(src), tgt.ctypes.data if tgt.size else None, len(tgt),
+            out.ctypes.data if out.size else None, int(device), ctypes.byref(info))
+    else:
+        out = np.empty((len(src), len(tgt)), dtype=np.uint32) if table else np.empty((2, len(src)), dtype=np.uint64)
+        info = DistInfo()
+        rc = lib.g2n_csr_pair_distances_host(
+            ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, n, len(ix),
+            src.ctypes.data if src.size else None, len(src), tgt.ctypes.data if tgt.size else None, len(tgt),
+            PAIR_TABLE if table else PAIR_SUMS, out.ctypes.data if out.size else None, int(device), ctypes.byref(info))
+    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
+        raise NotImplementedError(f"GPU pair distances: {last_error()}")
+    if rc == E_ARG:
+        raise ValueError(f"GPU pair distances: {last_error()}")
+    if rc != OK:
+        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+    return ((out,) if table else (out[0], out[1])), (_wdist_info(info) if weighted else _dist_info(info))
+
+
+def pair_distances_from_path(path: str, opts: Options, paths: "Paths", source: int, target: int):
+    """g2n_pair_distances_from_path for the paths ``source`` and ``target``: (the build's result without a
+    matrix, (S, C) — or, with opts.weight_tag, the float64 table (D,) —, the info fields, the orientation
+    flag, the first missing step of the source or -1, whether a stored weight is negative or not
+    finite).  The output is meaningful only when the status is OK, no step is missing and no weight is
+    bad."""
+    lib = load()
+    n_a = int(paths.path_ptr[source + 1] - paths.path_ptr[source])
+    n_b = int(paths.path_ptr[target + 1] - paths.path_ptr[target])
+    weighted = bool(opts.weight_tag)
+    out = np.full((n_a, n_b), np.inf, dtype=np.float64) if weighted else np.zeros((2, n_a), dtype=np.uint64)
+    info, winfo = DistInfo(), WDistInfo()
+    oriented, missing, bad = ctypes.c_int32(0), ctypes.c_int64(-1), ctypes.c_int32(0)
+    res = ctypes.POINTER(Result)()
+    rc = lib.g2n_pair_distances_from_path(os.fsencode(path), ctypes.byref(opts), paths._h, source, target,
+                                          PAIR_TABLE if weighted else PAIR_SUMS, out.ctypes.data if out.size else None,
+                                          ctypes.byref(info), ctypes.byref(winfo), ctypes.byref(oriented),
+                                          ctypes.byref(missing), ctypes.byref(bad), ctypes.byref(res))
+    tabs = (out,) if weighted else (out[0], out[1])
+    return (_from_result(res, rc), tabs, _wdist_info(winfo) if weighted else _dist_info(info), bool(oriented.value),
+            int(missing.value), bool(bad.value))
 
 
 class Paths:

@@ -918,6 +918,82 @@ def path_distances(A, paths, *, method: str = "min", weighted: bool = False, dev
     return (M, info) if return_info else M
 
 
+def _pair_csr(A, who: str, weighted: bool):
+    """``A`` as ``path_distances`` takes it: (indptr, indices, float64 data or None, n)."""
+    if not sp.issparse(A):
+        raise TypeError(f"{who} takes a scipy sparse matrix")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"{who} takes a square matrix")
+    data = None
+    if weighted:
+        A, data = _weighted_csr(A)
+    elif A.format != "csr":
+        # structure only: unit values in a dtype whose sums cannot overflow
+        C = A.tocoo()
+        A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
+        A.sum_duplicates()
+    n = int(A.shape[0])
+    if n >= 2**31 - 1:
+        raise NotImplementedError("GPU pair distances need node ids below 2^31 - 1")
+    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
+    return np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt), data, n
+
+
+def node_distances(A, sources, targets, *, weighted: bool = False, device: int = 0, return_info: bool = False):
+    """The node-to-node distance table over the graph of the square scipy sparse matrix ``A`` (taken as
+    ``path_distances`` takes it; extension): a ``(len(sources), len(targets))`` float64 array,
+    ``M[i][t]`` = the hops — with ``weighted=True`` the length of the shortest path over the stored
+    values, bit for bit Dijkstra's — from node ``sources[i]`` to node ``targets[t]``, 0.0 where they are
+    the same node, ``inf`` where there is no path.  Both lists keep their order and their duplicates;
+    ``-1`` is no node (a row or column of ``inf``), any other id outside ``[0, n)`` raises ValueError.
+    One bit-parallel search carries 64 sources (g2n_csr_pair_distances_host, g2n_pairs.hip).
+    ``return_info=True`` also returns the g2n_dist_info (weighted: g2n_wdist_info) fields."""
+    ip, ix, data, n = _pair_csr(A, "node_distances", weighted)
+    (D,), info = nat.csr_pair_distances_host(ip, ix, data, n, sources, targets, True, device)
+    if not weighted:
+        M = D.astype(np.float64)
+        M[D == np.uint32(0xFFFFFFFF)] = np.inf
+        D = M
+    return (D, info) if return_info else D
+
+
+def pair_sums(A, sources, targets, *, device: int = 0, return_info: bool = False):
+    """``(S, C)``, uint64 arrays of ``len(sources)``: ``C[i]`` = how many entries of ``targets`` node
+    ``sources[i]`` reaches (itself included, each occurrence counted), ``S[i]`` = the sum of their hop
+    distances — the row sums of ``node_distances`` over its finite cells, without the table: the
+    accumulators are O(len(sources)) whatever ``len(targets)`` (extension; G2N_PAIR_SUMS).  Lists as
+    ``node_distances`` takes them."""
+    ip, ix, _data, n = _pair_csr(A, "pair_sums", False)
+    (S, C), info = nat.csr_pair_distances_host(ip, ix, None, n, sources, targets, False, device)
+    return (S, C, info) if return_info else (S, C)
+
+
+def mean_of_sums(S, C) -> float:
+    """genome_distance(method="mean") from G2N_PAIR_SUMS' sums and counts: ``float(total) / count`` with
+    ``total`` and ``count`` as Python ints — the reference's float total is exact below 2^53 —;
+    NetworkXNoPath when nothing is reached."""
+    total, count = int(np.sum(S, dtype=object)) if len(S) else 0, int(np.sum(C, dtype=object)) if len(C) else 0
+    if count == 0:
+        raise NetworkXNoPath("no path between node sets")
+    if total >= 2**53:
+        raise NotImplementedError("a distance sum of 2^53 or more is not exact in float64")
+    return float(total) / count
+
+
+def mean_of_table(D) -> float:
+    """genome_distance(method="mean") over a weighted graph from the float64 table: the reference's
+    running total in its order of additions (analysis.py:148-156: u outer, v inner, from 0.0, the
+    unreachable pairs skipped), divided by the count; NetworkXNoPath when nothing is reached."""
+    total, count = 0.0, 0
+    for d in np.asarray(D, dtype=np.float64).reshape(-1).tolist():
+        if d != np.inf:
+            total += d
+            count += 1
+    if count == 0:
+        raise NetworkXNoPath("no path between node sets")
+    return total / count
+
+
 def _stats_one_piece(path, device: int, who: str = "compute_stats", then: str = "graph_stats") -> None:
     """compute_stats (and the path distances) build the file in one piece on one GPU: an input
     parse_gfa would build in chunks (its working set past the GPU's free HBM) is outside them."""
@@ -1149,7 +1225,10 @@ def genome_distance_matrix(gfa_path, method: str = "min", *, raw_bytes_id: bool 
     return (M, info) if return_info else M
 
 
-def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id: bool = False,
+_QUADRATIC_WARNING = "Mean distance scales quadratically; this may be very slow on large sets"
+
+
+def genome_distance(path, name_a, name_b, *, method: str = "min", directed: bool = True, raw_bytes_id: bool = False,
                     verbose: bool = False, device: int = 0, weight_tag=None):
     """``gfa2network distance GFA --path A B`` as a function (cli.py:323-346): the fewest hops from
     a step of path ``name_a`` to a step of path ``name_b`` (an int; the search runs from A only) over
@@ -1160,7 +1239,20 @@ def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id
     ``weight_tag`` (extension; ``None`` or ``""``: the hops above, an int, unchanged): the length of
     the shortest path over the graph ``parse_gfa(path, build_graph=True, directed=...,
     weight_tag=...)`` builds, as ``genome_distance_matrix`` describes — always a ``float`` (the
-    reference returns an equal ``int`` when the best path crosses untagged edges only)."""
+    reference returns an equal ``int`` when the best path crosses untagged edges only).
+
+    ``method="mean"`` (analysis.py:142-159): the mean of the shortest-path lengths over every pair (u in
+    A, v in B) that has a path, each occurrence of a step counted, a ``float``.  One bit-parallel search
+    carries 64 steps of A (g2n_pairs.hip), so the |A| x |B| searches of the reference are ceil(|A| / 64)
+    passes over the CSR; only |A| sums and counts come back.  Hops: ``float(total) / count`` from
+    integer sums (NotImplementedError at a total of 2^53 or more).  With ``weight_tag``: the float64
+    table comes back and is folded here in the reference's order of additions.  After the orientation
+    warning the reference's RuntimeWarning about quadratic cost is raised past 1000 pairs, unless
+    ``GFANET_DISABLE_WARNINGS=1`` — callers filter on it; the cost it speaks of is not this search's.
+    NetworkXNoPath when a path is empty or no pair has a path, else NodeNotFound for the first step of A
+    that is no node; a step of B that is none is never reached.  Any other ``method`` raises
+    ValueError(f"unknown method: {method}") where the reference does: after the build's own errors and
+    warnings."""
     p = _named_file(path, "genome_distance")
     _stats_one_piece(p, device, "genome_distance", "path_distances")
     ps = nat.Paths(p)
@@ -1181,7 +1273,12 @@ def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id
         _load_paths_pass(raw, ps, raw_bytes_id, path)
         raise KeyError(name_a if a is None else name_b)
     bad = False
-    if weight_tag:
+    if method == "mean":
+        wopts = _dist_opts(directed, raw_bytes_id, device, weight_tag) if weight_tag else opts
+        raw, tabs, _info, oriented, missing, bad = nat.pair_distances_from_path(p, wopts, ps, a, b)
+        _load_paths_pass(_paths_raw(raw, p, directed, raw_bytes_id, device) if weight_tag else raw, ps, raw_bytes_id,
+                         path)
+    elif weight_tag:
         raw, tabs, _info, oriented, missing, bad = nat.wdistances_from_path(
             p, _dist_opts(directed, raw_bytes_id, device, weight_tag), ps, a, b, False)
         _load_paths_pass(_paths_raw(raw, p, directed, raw_bytes_id, device), ps, raw_bytes_id, path)
@@ -1191,8 +1288,20 @@ def genome_distance(path, name_a, name_b, *, directed: bool = True, raw_bytes_id
     _graph_pass(raw, raw_bytes_id, verbose, path)
     if directed:
         _warn_oriented(raw, oriented)
+    if method not in ("min", "mean"):
+        raise ValueError(f"unknown method: {method}")
     if bad:
         raise NotImplementedError(_BAD_WEIGHT)
+    if method == "mean":
+        n_a = int(ps.path_ptr[a + 1] - ps.path_ptr[a])
+        n_b = int(ps.path_ptr[b + 1] - ps.path_ptr[b])
+        if n_a * n_b > 1000 and os.getenv("GFANET_DISABLE_WARNINGS") != "1":
+            warnings.warn(_QUADRATIC_WARNING, RuntimeWarning, stacklevel=2)
+        if n_a == 0 or n_b == 0:
+            raise NetworkXNoPath("no path between node sets")
+        if missing >= 0:
+            raise _missing_step(ps.step(int(ps.path_ptr[a]) + missing), raw_bytes_id)
+        return mean_of_table(tabs[0]) if weight_tag else mean_of_sums(*tabs)
     if missing >= 0:
         raise _missing_step(ps.step(int(ps.path_ptr[a]) + missing), raw_bytes_id)
     if weight_tag:

@@ -10,7 +10,9 @@ document (``export_graph_json``); ``stats`` (cli.py:152-159, 364-376) prints
 --seq`` and ``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same
 CSR (``--seq`` finds the nodes that carry the two sequences there too: ``sequence_distance``; an input
 that is no named file is a usage error, exit status 2, where the function raises the reference's
-FileNotFoundError).  As in
+FileNotFoundError).  ``distance --path
+A B --method mean`` (extension; the default ``min`` prints what it printed) is ``genome_distance(...,
+method="mean")``.  As in
 the reference, ``distance`` and ``distance-matrix`` have no ``--weight-tag``: the functions take
 ``weight_tag=``.  Graph outputs (``--graph``, export graphml / gexf) are outside the GPU
 GFA->CSR path.
@@ -27,7 +29,9 @@ from .api import (compute_stats, convert_format, export_edge_list, export_graph_
                   parse_gfa_names, save_matrix, save_node_map_native, sequence_distance)
 
 
-def _parser() -> argparse.ArgumentParser:
+def _parser(extensions: bool = False) -> argparse.ArgumentParser:
+    """The reference's parser (its flags, nothing else below the global ``--device``); ``extensions``:
+    plus this build's own subcommand flags — ``distance --method`` — as ``main`` parses."""
     parser = argparse.ArgumentParser(prog="gfa2network")
     parser.add_argument("--version", action="version", version=f"gfa2network-amd {__version__}")
     parser.add_argument("--raw-bytes-id", action="store_true", help="Use raw bytes for node identifiers (legacy)")
@@ -81,6 +85,9 @@ def _parser() -> argparse.ArgumentParser:
     g4.add_argument("--directed", dest="directed", action="store_true", default=True)
     g4.add_argument("--undirected", dest="directed", action="store_false")
     p_dist.add_argument("--backend", choices=["networkx", "igraph"], default="networkx", help="Graph backend to use")
+    if extensions:
+        p_dist.add_argument("--method", choices=["min", "mean"], default="min",
+                            help="--path: the minimal distance, or the mean over all node pairs (GPU build option)")
     p_dist.add_argument("--verbose", action="store_true")
     p_dm = sub.add_parser("distance-matrix", help="Pairwise distances between paths")  # cli.py:177-189
     p_dm.add_argument("gfa", help="Input *.gfa* file")
@@ -92,7 +99,7 @@ def _parser() -> argparse.ArgumentParser:
 
 
 def main(argv: list[str] | None = None) -> None:
-    parser = _parser()
+    parser = _parser(extensions=True)
     args = parser.parse_args(argv)
     if args.cmd == "export":
         if args.format == "json":  # cli.py:282-306
@@ -120,6 +127,8 @@ def main(argv: list[str] | None = None) -> None:
         if args.backend == "igraph":
             parser.error("--backend igraph is outside the GPU GFA->CSR path")
         if args.seq:  # cli.py:308-321
+            if args.method != "min":
+                parser.error("distance --method mean takes --path (sequence_distance has no method)")
             seq_a, seq_b = args.seq
             # sequence_distance matches the sequences in the file's staged bytes: it takes a named file,
             # not stdin.  An input that is none is a usage error here, before a GPU is touched (the
@@ -132,8 +141,8 @@ def main(argv: list[str] | None = None) -> None:
         name_a, name_b = args.path
         try:
             dist = genome_distance(args.gfa, name_a.encode() if args.raw_bytes_id else name_a,
-                                   name_b.encode() if args.raw_bytes_id else name_b, directed=args.directed,
-                                   raw_bytes_id=args.raw_bytes_id, verbose=args.verbose, device=args.device)
+                                   name_b.encode() if args.raw_bytes_id else name_b, method=args.method,
+                                   directed=args.directed, raw_bytes_id=args.raw_bytes_id, verbose=args.verbose, device=args.device)
         except KeyError as exc:
             if type(exc) is not KeyError:  # (a NodeNotFound defined without networkx)
                 raise

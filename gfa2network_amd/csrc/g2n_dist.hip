@@ -23,8 +23,9 @@
 //           after the level's expansion: seen / next are complete then, and the wide collect
 //           rebuilds the frontier from next.
 //   The two regimes' walks, queues and hand-over are the frontier_* templates below, which the
-//   weighted search (g2n_wdist.hip) runs with its own row bodies; the host's loop over them is
-//   run_frontier (g2n_queries.hip).
+//   weighted search (g2n_wdist.hip) runs with its own row bodies and the node-to-node search
+//   (g2n_pairs.hip) with its own accumulation; the host's loop over them is run_frontier
+//   (g2n_queries.hip).
 // Accumulation, when v enters the frontier at level L with new bits B, for v's membership entries j:
 //   min   todo = B & ~done[j] (one load); if any, the bits the atomicOr on done[j] newly set store L
 //         into D[i][j] — each cell is written once, by one thread.

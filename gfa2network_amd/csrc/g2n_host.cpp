@@ -395,7 +395,7 @@ static bool dist_build_opts(const g2n_options* opts, bool weighted, g2n_options*
 static int distances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
                                int64_t target, int32_t mode, void* out_tables, g2n_dist_info* info,
                                g2n_wdist_info* winfo, int32_t* oriented, int64_t* missing_step, int32_t* bad_weight,
-                               g2n_result** res) {
+                               g2n_result** res, bool pairs = false) {
   if (!res || !path || !paths || (!info && !winfo) || !oriented || !missing_step || (winfo && !bad_weight))
     return G2N_E_ARG;
   *res = nullptr;
@@ -435,7 +435,8 @@ static int distances_from_path(const char* path, const g2n_options* opts, const 
     req.n_steps = pair_offs.size() - 1;
     req.n_source_steps = (uint64_t)pair_ptr[1];
   }
-  if (req.K && !out_tables) return G2N_E_ARG;
+  if (req.K && !out_tables && !pairs) return G2N_E_ARG;  // (a pair request of no sources has no output)
+  req.pairs = pairs;
   req.mode = mode;
   req.check_ascii = opts->want_node_names != 0;
   req.names_if_high = !req.check_ascii && o.directed;
@@ -469,6 +470,18 @@ int g2n_wdistances_from_path(const char* path, const g2n_options* opts, const g2
   if (!info) return G2N_E_ARG;
   return distances_from_path(path, opts, paths, source, target, mode, out_tables, nullptr, info, oriented, missing_step,
                              bad_weight, res);
+}
+
+int g2n_pair_distances_from_path(const char* path, const g2n_options* opts, const g2n_paths* paths, int64_t source,
+                                 int64_t target, int32_t mode, void* out, g2n_dist_info* info, g2n_wdist_info* winfo,
+                                 int32_t* oriented, int64_t* missing_step, int32_t* bad_weight, g2n_result** res) {
+  if (!opts || source < 0) return G2N_E_ARG;
+  const bool weighted = opts->weight_tag && *opts->weight_tag;
+  if (weighted ? (!winfo || !bad_weight || mode != G2N_PAIR_TABLE)
+               : (!info || (mode != G2N_PAIR_SUMS && mode != G2N_PAIR_TABLE)))
+    return G2N_E_ARG;
+  return distances_from_path(path, opts, paths, source, target, mode, out, weighted ? nullptr : info,
+                             weighted ? winfo : nullptr, oriented, missing_step, bad_weight, res, true);
 }
 
 int g2n_graph_weights_from_path(const char* path, const g2n_options* opts, g2n_result** res) {

@@ -130,6 +130,9 @@ struct DistRequest {
   // searches its values; mode may be G2N_DIST_MEAN_FOLD.  winfo replaces info (null then).
   g2n_wdist_info* winfo;      // non-null: the weighted request
   int32_t* bad_weight;        // out: 1 when a stored value is negative or not finite (nothing was searched then)
+  // g2n_pair_distances_from_path: K = 2, and the two paths' steps are the sources and the targets of
+  // g2n_csr_pair_distances(_weighted); mode is a G2N_PAIR_* then and tables that call's output.
+  bool pairs;
 };
 void set_dist_request(const DistRequest* req);  // nullptr: none (thread-local)
 

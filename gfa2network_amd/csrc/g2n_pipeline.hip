@@ -27,6 +27,7 @@
 #include "g2n_stats.hip"
 #include "g2n_dist.hip"
 #include "g2n_wdist.hip"
+#include "g2n_pairs.hip"
 #include "g2n_seq.hip"
 
 #define G2N_HIP(call)                                                                                      \
@@ -3335,6 +3336,46 @@ int g2n_csr_path_distances_weighted_host(const void* indptr, const void* indices
   return g2n::guarded([&] {
     return g2n::csr_path_distances_weighted_host(indptr, indices, index_width, values, n, nnz, path_ptr, path_nodes, K,
                                                  mode, out_tables, device, info);
+  });
+}
+
+int g2n_csr_pair_distances(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width, uint64_t n,
+                           uint64_t nnz, const int64_t* d_sources, uint64_t n_src, const int64_t* d_targets,
+                           uint64_t n_tgt, int32_t mode, void* d_out, g2n_dist_info* info) {
+  if (!info) return G2N_E_ARG;
+  G2N_CTX_CALL(ctx, g2n::pair_distances(ctx, d_indptr, d_indices, index_width, n, nnz, d_sources, n_src, d_targets, n_tgt,
+                                        mode, d_out, info));
+  return G2N_OK;
+}
+
+int g2n_csr_pair_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                                const int64_t* sources, uint64_t n_src, const int64_t* targets, uint64_t n_tgt,
+                                int32_t mode, void* out, int32_t device, g2n_dist_info* info) {
+  if (!info) return G2N_E_ARG;
+  return g2n::guarded([&] {
+    return g2n::csr_pair_distances_host(indptr, indices, index_width, n, nnz, sources, n_src, targets, n_tgt, mode, out,
+                                        device, info);
+  });
+}
+
+int g2n_csr_pair_distances_weighted(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width,
+                                    const double* d_values, uint64_t n, uint64_t nnz, const int64_t* d_sources,
+                                    uint64_t n_src, const int64_t* d_targets, uint64_t n_tgt, void* d_out,
+                                    g2n_wdist_info* info) {
+  if (!info) return G2N_E_ARG;
+  G2N_CTX_CALL(ctx, g2n::wpair_distances(ctx, d_indptr, d_indices, index_width, d_values, n, nnz, d_sources, n_src,
+                                         d_targets, n_tgt, d_out, info));
+  return G2N_OK;
+}
+
+int g2n_csr_pair_distances_weighted_host(const void* indptr, const void* indices, int32_t index_width,
+                                         const double* values, uint64_t n, uint64_t nnz, const int64_t* sources,
+                                         uint64_t n_src, const int64_t* targets, uint64_t n_tgt, void* out,
+                                         int32_t device, g2n_wdist_info* info) {
+  if (!info) return G2N_E_ARG;
+  return g2n::guarded([&] {
+    return g2n::csr_pair_distances_weighted_host(indptr, indices, index_width, values, n, nnz, sources, n_src, targets,
+                                                 n_tgt, out, device, info);
   });
 }
 

@@ -1,6 +1,7 @@
 // g2n_queries.hip — the queries over a finished, device-resident CSR: graph statistics
 // (g2n_csr_stats), hop distances between paths (g2n_csr_path_distances: g2n_dist.hip), weighted ones
-// (g2n_csr_path_distances_weighted: g2n_wdist.hip), and what a host build returns in place of its
+// (g2n_csr_path_distances_weighted: g2n_wdist.hip), node-to-node distances (g2n_csr_pair_distances and
+// its weighted twin: g2n_pairs.hip), and what a host build returns in place of its
 // matrix when a stats / distance / sequence-distance request is set (g2n_host.cpp).
 //
 // Part of g2n_pipeline.hip's translation unit, included where the host results begin: it uses that
@@ -374,26 +375,29 @@ static void path_distances(g2n_context* c, const void* indptr, const void* indic
 }
 
 // ------------------------------------------------ weighted path distances ------
-// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
-// tables: device.  Nothing is written to the tables before every array has passed its check.
-template <class I>
-static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
-                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
-                              uint64_t steps, int32_t mode, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
-  const std::string who = "g2n_csr_path_distances_weighted";
-  const bool mean = mode != G2N_DIST_MIN, fold = mode == G2N_DIST_MEAN_FOLD;
-  auto* st = dget<DistState>(c, S_DSTATE, 1);
-  G2N_HIP(hipEventRecord(ev[0], c->stream));
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
-  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
-  check_on_device(c, who, indptr, indices, values, n, nnz, path_ptr, path_nodes, K, steps, step_path, cnt, st);
-  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
-  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
-  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
-  const uint64_t long_cap = nnz / kStatsShortRow + 1;
-  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
-  // ---- B paths a batch: B * n distances must fit what is free (and what the slot already holds)
+// what one weighted search works in, beside its distances (the arena's S_D* slots)
+struct WSearchBufs {
+  DistState* st;
+  unsigned long long* next;
+  uint32_t* queue;
+  unsigned long long* qmask;
+  uint32_t* long_rows;
+  uint64_t long_cap;
+};
+
+static WSearchBufs wsearch_bufs(g2n_context* c, uint64_t n, uint64_t nnz) {
+  WSearchBufs w{};
+  w.st = dget<DistState>(c, S_DSTATE, 1);
+  w.next = dget<unsigned long long>(c, S_DNEXT, n);
+  w.queue = dget<uint32_t>(c, S_DQUEUE, n);
+  w.qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  w.long_cap = nnz / kStatsShortRow + 1;
+  w.long_rows = dget<uint32_t>(c, S_DLONG, w.long_cap);
+  return w;
+}
+
+// B searches a batch, of K wanted: B * n distances must fit what is free (and what the slot already holds)
+static uint64_t wdist_batch_width(g2n_context* c, const std::string& who, uint64_t n, uint64_t K) {
   uint64_t B = std::min<uint64_t>(64, K);
   if (n) {
     size_t f = 0, t = 0;
@@ -404,6 +408,55 @@ static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices,
       throw Failure(G2N_E_UNSUPPORTED, who + ": the distances of one path over " + std::to_string(n) +
                                            " nodes exceed the device's free memory");
   }
+  return B;
+}
+
+// One batch's weighted search, from the sources already in dist (0.0) and next (their bits; any: there
+// are some): round R expands the nodes that round R - 1 improved (round 0: the sources).  Returns the
+// last round that improved a distance.
+template <class I>
+static uint32_t wdist_search(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
+                             const double* values, uint64_t n, uint64_t nnz, uint64_t B, unsigned long long* dist,
+                             const WSearchBufs& w, bool any, int64_t* launches) {
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  const unsigned gn = std::min(grid_for(n), gcap);
+  return run_frontier(
+      c, who, w.st, n, any, launches,
+      [&](uint32_t R) {
+        hipLaunchKernelGGL(k_wdist_collect, dim3(gn), dim3(256), 0, c->stream, w.next, n, R, w.queue, w.qmask, w.st);
+      },
+      [&](uint32_t count) {
+        hipLaunchKernelGGL(k_wdist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
+                           indices, values, n, nnz, (uint32_t)B, dist, w.next, (const uint32_t*)w.queue,
+                           (const unsigned long long*)w.qmask, w.long_rows, w.long_cap, w.st);
+        hipLaunchKernelGGL(k_wdist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices,
+                           values, n, nnz, (uint32_t)B, dist, w.next, (const uint32_t*)w.queue,
+                           (const unsigned long long*)w.qmask, (const uint32_t*)w.long_rows, w.long_cap, w.st);
+      },
+      [&](uint32_t budget) {
+        hipLaunchKernelGGL(k_wdist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, values, n,
+                           nnz, (uint32_t)B, dist, w.next, w.queue, w.qmask, w.st, budget);
+      });
+}
+
+// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
+// tables: device.  Nothing is written to the tables before every array has passed its check.
+template <class I>
+static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
+                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
+                              uint64_t steps, int32_t mode, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
+  const std::string who = "g2n_csr_path_distances_weighted";
+  const bool mean = mode != G2N_DIST_MIN, fold = mode == G2N_DIST_MEAN_FOLD;
+  const WSearchBufs w = wsearch_bufs(c, n, nnz);
+  DistState* st = w.st;
+  unsigned long long* next = w.next;
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
+  check_on_device(c, who, indptr, indices, values, n, nnz, path_ptr, path_nodes, K, steps, step_path, cnt, st);
+  // ---- B paths a batch
+  const uint64_t B = wdist_batch_width(c, who, n, K);
   auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
   info->batch_paths = (int64_t)B;
   // ---- tables
@@ -414,7 +467,6 @@ static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices,
   std::vector<int64_t> h_ptr(K + 1);
   G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   G2N_HIP(hipStreamSynchronize(c->stream));
-  const unsigned gn = std::min(grid_for(n), gcap);
   int64_t launches = 0, rounds = 0, batches = 0;
   double ms_search = 0.0, ms_tables = 0.0;
   const uint64_t n_batches = (K + B - 1) / B;
@@ -434,24 +486,7 @@ static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices,
                          (const uint32_t*)step_path, (uint32_t)base, (uint32_t)B, dist, next);
       launches++;
     }
-    // round R expands the nodes that round R - 1 improved (round 0: the sources)
-    const uint32_t last = run_frontier(
-        c, who, st, n, s1 > s0, &launches,
-        [&](uint32_t R) {
-          hipLaunchKernelGGL(k_wdist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, R, queue, qmask, st);
-        },
-        [&](uint32_t count) {
-          hipLaunchKernelGGL(k_wdist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
-                             indices, values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
-                             (const unsigned long long*)qmask, long_rows, long_cap, st);
-          hipLaunchKernelGGL(k_wdist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices,
-                             values, n, nnz, (uint32_t)B, dist, next, (const uint32_t*)queue,
-                             (const unsigned long long*)qmask, (const uint32_t*)long_rows, long_cap, st);
-        },
-        [&](uint32_t budget) {
-          hipLaunchKernelGGL(k_wdist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, values, n,
-                             nnz, (uint32_t)B, dist, next, queue, qmask, st, budget);
-        });
+    const uint32_t last = wdist_search(c, who, indptr, indices, values, n, nnz, B, dist, w, s1 > s0, &launches);
     rounds = std::max<int64_t>(rounds, last);
     // ---- the batch's rows of the tables
     G2N_HIP(hipEventRecord(ev[1], c->stream));
@@ -550,6 +585,273 @@ int csr_path_distances_weighted_host(const void* indptr, const void* indices, in
                           wpath_distances(c, d.indptr, d.indices, index_width, d.values, n, nnz, dpp, dpn, K, mode, dtab,
                                           info);
                         });
+}
+
+// ------------------------------------------------ node-to-node distances (g2n_pairs.hip) ------
+static void check_pair_call(const std::string& who, int32_t mode, bool weighted, uint64_t n_src, uint64_t n_tgt) {
+  if (mode != G2N_PAIR_TABLE && (weighted || mode != G2N_PAIR_SUMS)) throw Failure(G2N_E_ARG, who + ": unknown mode");
+  if (n_src >= 0xFFFFFFFFull || n_tgt >= 0xFFFFFFFFull)
+    throw Failure(G2N_E_UNSUPPORTED, who + ": 2^32-1 or more sources or targets");
+}
+
+// bytes of one call's output — sums: S and C, n_src uint64 each; table: n_src x n_tgt cells of 4 (hops)
+// or 8 (weighted) bytes; ~0 = past 2^63
+static uint64_t pair_out_bytes(int32_t mode, bool weighted, uint64_t n_src, uint64_t n_tgt) {
+  if (mode == G2N_PAIR_SUMS) return n_src * 16;
+  if (n_src && n_tgt > (1ull << 60) / n_src) return ~0ull;
+  return n_src * n_tgt * (weighted ? 8 : 4);
+}
+
+// an output this library allocates must fit the device's free memory
+static void check_pair_out(const std::string& who, uint64_t bytes) {
+  size_t f = 0, t = 0;
+  G2N_HIP(hipMemGetInfo(&f, &t));
+  if (bytes > f)
+    throw Failure(G2N_E_UNSUPPORTED, who + ": the distance table exceeds the device's free memory");
+}
+
+// The caller's arrays, checked whole on the device before anything is searched or written (values:
+// null for hops); the targets' occurrences per node into tcnt (n + 1, cleared here; null: not wanted).
+template <class I>
+static void pair_check_on_device(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
+                                 const double* values, uint64_t n, uint64_t nnz, const int64_t* sources, uint64_t n_src,
+                                 const int64_t* targets, uint64_t n_tgt, uint32_t* tcnt, DistState* st) {
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+  if (tcnt) G2N_HIP(hipMemsetAsync(tcnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
+                     indices, n, nnz, st);
+  if (values && nnz)
+    hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for(nnz), gcap)), dim3(256), 0, c->stream, values, nnz, st);
+  if (n_src)
+    hipLaunchKernelGGL(k_pair_ids, dim3(grid_for(n_src)), dim3(256), 0, c->stream, sources, n_src, n,
+                       (uint32_t*)nullptr, st);
+  if (n_tgt)
+    hipLaunchKernelGGL(k_pair_ids, dim3(grid_for(n_tgt)), dim3(256), 0, c->stream, targets, n_tgt, n, tcnt, st);
+  if (read_dev(c, st).bad)
+    throw Failure(G2N_E_ARG, who + ": indptr / indices / sources / targets out of range" +
+                                 (values ? ", or a value that is negative or not finite" : ""));
+}
+
+// g2n_csr_pair_distances on c's stream (the caller holds c's lock and opened the call); out: device.
+template <class I>
+static void pair_distances_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz,
+                             const int64_t* sources, uint64_t n_src, const int64_t* targets, uint64_t n_tgt, bool table,
+                             void* out, g2n_dist_info* info) {
+  const std::string who = "g2n_csr_pair_distances";
+  auto* st = dget<DistState>(c, S_DSTATE, 1);
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  auto* tcnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  pair_check_on_device(c, who, indptr, indices, (const double*)nullptr, n, nnz, sources, n_src, targets, n_tgt, tcnt,
+                       st);
+  PairAcc acc{};
+  acc.n_tgt = n_tgt;
+  if (table) {  // the targets' positions sorted by node
+    auto* mem_ptr = dget<uint32_t>(c, S_DMPTR, n + 1);
+    auto* cursor = dget<uint32_t>(c, S_DCUR, n + 1);
+    auto* mem_pos = dget<uint32_t>(c, S_DMPATH, n_tgt);
+    scan_excl<uint32_t, uint32_t>(c, tcnt, mem_ptr, n + 1);
+    G2N_HIP(hipMemcpyAsync(cursor, mem_ptr, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (n_tgt)
+      hipLaunchKernelGGL(k_pair_fill, dim3(grid_for(n_tgt)), dim3(256), 0, c->stream, targets, n_tgt, n, cursor,
+                         mem_pos);
+    acc.mem_ptr = mem_ptr;
+    acc.mem_pos = mem_pos;
+    acc.D = (uint32_t*)out;
+    if (n_src && n_tgt) G2N_HIP(hipMemsetAsync(out, 0xFF, n_src * n_tgt * 4, c->stream));
+  } else {
+    acc.tcnt = tcnt;
+    acc.S = (unsigned long long*)out;
+    acc.C = acc.S + n_src;
+    if (n_src) G2N_HIP(hipMemsetAsync(out, 0, n_src * 16, c->stream));
+  }
+  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
+  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
+  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
+  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
+  const unsigned gn = std::min(grid_for(n), gcap);
+  int64_t launches = 0, levels = 0, batches = 0;
+  for (uint64_t base = 0; base < n_src; base += 64, batches++) {
+    acc.base = base;
+    acc.nb = (uint32_t)std::min<uint64_t>(64, n_src - base);
+    G2N_HIP(hipMemsetAsync(seen, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+    if (n) {
+      hipLaunchKernelGGL(k_pair_sources, dim3(1), dim3(64), 0, c->stream, sources, base, base + acc.nb, n, seen, next);
+      launches++;
+    }
+    const uint32_t last = run_frontier(
+        c, who, st, n, n != 0, &launches,
+        [&](uint32_t L) {
+          if (table)
+            hipLaunchKernelGGL(k_pair_collect<true>, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc, st);
+          else
+            hipLaunchKernelGGL(k_pair_collect<false>, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc,
+                               st);
+        },
+        [&](uint32_t count) {
+          hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
+                             indices, n, nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
+                             long_rows, long_cap, st);
+          hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
+                             nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
+                             (const uint32_t*)long_rows, long_cap, st);
+        },
+        [&](uint32_t budget) {
+          if (table)
+            hipLaunchKernelGGL((k_pair_narrow<I, true>), dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n,
+                               nnz, seen, next, queue, qmask, acc, st, budget);
+          else
+            hipLaunchKernelGGL((k_pair_narrow<I, false>), dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n,
+                               nnz, seen, next, queue, qmask, acc, st, budget);
+        });
+    levels = std::max<int64_t>(levels, last);
+  }
+  info->levels = levels;
+  info->launches = launches;
+  info->batches = batches;
+}
+
+static void pair_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
+                           uint64_t nnz, const int64_t* sources, uint64_t n_src, const int64_t* targets, uint64_t n_tgt,
+                           int32_t mode, void* out, g2n_dist_info* info) {
+  const std::string who = "g2n_csr_pair_distances";
+  std::memset(info, 0, sizeof(*info));
+  check_pair_call(who, mode, false, n_src, n_tgt);
+  const bool wants_out = pair_out_bytes(mode, false, n_src, n_tgt) != 0;
+  check_csr(who, index_width, n, nnz, (!n_src || sources) && (!n_tgt || targets) && (!wants_out || out) && (!n || indptr),
+            indices, true);
+  Events<2> ev;
+  ev.create();
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
+    pair_distances_t(c, ip, ix, n, nnz, sources, n_src, targets, n_tgt, mode == G2N_PAIR_TABLE, out, info);
+  });
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  info->ms_bfs = ms;
+}
+
+// g2n_csr_pair_distances_weighted on c's stream; out: device, n_src x n_tgt float64, not written unless
+// every array passed its check.
+template <class I>
+static void wpair_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
+                              uint64_t nnz, const int64_t* sources, uint64_t n_src, const int64_t* targets,
+                              uint64_t n_tgt, void* out, g2n_wdist_info* info, hipEvent_t* ev) {
+  const std::string who = "g2n_csr_pair_distances_weighted";
+  const WSearchBufs w = wsearch_bufs(c, n, nnz);
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  pair_check_on_device(c, who, indptr, indices, values, n, nnz, sources, n_src, targets, n_tgt, (uint32_t*)nullptr,
+                       w.st);
+  if (n_src == 0 || n_tgt == 0) return;
+  const uint64_t B = wdist_batch_width(c, who, n, n_src);
+  auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
+  info->batch_paths = (int64_t)B;
+  int64_t launches = 0, rounds = 0, batches = 0;
+  double ms_search = 0.0, ms_tables = 0.0;
+  for (uint64_t base = 0; base < n_src; base += B, batches++) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_src - base);
+    if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
+    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(n * B), gcap)), dim3(256), 0, c->stream, dist, n * B,
+                       kWDistInf);
+    G2N_HIP(hipMemsetAsync(w.next, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(w.st, 0, sizeof(DistState), c->stream));
+    launches++;
+    if (n) {
+      hipLaunchKernelGGL(k_pair_wsources, dim3(1), dim3(64), 0, c->stream, sources, base, nb, n, (uint32_t)B, dist,
+                         w.next);
+      launches++;
+    }
+    const uint32_t last = wdist_search(c, who, indptr, indices, values, n, nnz, B, dist, w, n != 0, &launches);
+    rounds = std::max<int64_t>(rounds, last);
+    G2N_HIP(hipEventRecord(ev[1], c->stream));
+    hipLaunchKernelGGL(k_pair_wgather, dim3(std::min(grid_for(n_tgt * nb), gcap)), dim3(256), 0, c->stream, targets,
+                       n_tgt, n, (const unsigned long long*)dist, (uint32_t)B, nb, base, (unsigned long long*)out);
+    launches++;
+    G2N_HIP(hipEventRecord(ev[2], c->stream));
+    G2N_HIP(hipEventSynchronize(ev[2]));
+    float ms = 0.f;
+    G2N_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    ms_search += ms;
+    G2N_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    ms_tables += ms;
+  }
+  info->rounds = rounds;
+  info->launches = launches;
+  info->batches = batches;
+  info->ms_search = ms_search;
+  info->ms_tables = ms_tables;
+}
+
+static void wpair_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width,
+                            const double* values, uint64_t n, uint64_t nnz, const int64_t* sources, uint64_t n_src,
+                            const int64_t* targets, uint64_t n_tgt, void* out, g2n_wdist_info* info) {
+  const std::string who = "g2n_csr_pair_distances_weighted";
+  std::memset(info, 0, sizeof(*info));
+  info->batch_paths = (int64_t)std::max<uint64_t>(1, std::min<uint64_t>(64, n_src));
+  check_pair_call(who, G2N_PAIR_TABLE, true, n_src, n_tgt);
+  check_csr(who, index_width, n, nnz,
+            (!n_src || sources) && (!n_tgt || targets) && (!n_src || !n_tgt || out) && (!n || indptr), indices && values,
+            true);
+  Events<3> ev;
+  ev.create();
+  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
+    wpair_distances_t(c, ip, ix, values, n, nnz, sources, n_src, targets, n_tgt, out, info, ev.e);
+  });
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// The two pair _host entries: the CSR (values: null for hops), the two lists (S_DPN: the sources, then
+// the targets) and the output (S_DTAB) on the shared context, search(c, csr, sources, targets, out) on
+// them, and the output copied back.
+template <class Search>
+static int pairs_host(const std::string& who, const void* indptr, const void* indices, int32_t index_width,
+                      const double* values, bool weighted, uint64_t n, uint64_t nnz, const int64_t* sources,
+                      uint64_t n_src, const int64_t* targets, uint64_t n_tgt, int32_t mode, void* out, int32_t device,
+                      Search&& search) {
+  check_pair_call(who, mode, weighted, n_src, n_tgt);
+  const uint64_t bytes = pair_out_bytes(mode, weighted, n_src, n_tgt);
+  check_csr(who, index_width, n, nnz, indptr && (!n_src || sources) && (!n_tgt || targets) && (!bytes || out),
+            indices && (!weighted || values), false);
+  return host_call(device, [&](g2n_context* c) {
+    check_pair_out(who, bytes);
+    const StagedCsr d = stage_csr(c, indptr, indices, values, index_width, n, nnz);
+    auto* ids = dget<int64_t>(c, S_DPN, n_src + n_tgt);
+    void* dout = dbuf(c, S_DTAB, (size_t)bytes);
+    if (n_src) G2N_HIP(hipMemcpyAsync(ids, sources, (size_t)n_src * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_tgt) G2N_HIP(hipMemcpyAsync(ids + n_src, targets, (size_t)n_tgt * 8, hipMemcpyHostToDevice, c->stream));
+    search(c, d, ids, ids + n_src, dout);
+    if (bytes) G2N_HIP(hipMemcpyAsync(out, dout, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+int csr_pair_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                            const int64_t* sources, uint64_t n_src, const int64_t* targets, uint64_t n_tgt, int32_t mode,
+                            void* out, int32_t device, g2n_dist_info* info) {
+  return pairs_host("g2n_csr_pair_distances_host", indptr, indices, index_width, nullptr, false, n, nnz, sources, n_src,
+                    targets, n_tgt, mode, out, device,
+                    [&](g2n_context* c, const StagedCsr& d, const int64_t* ds, const int64_t* dt, void* dout) {
+                      pair_distances(c, d.indptr, d.indices, index_width, n, nnz, ds, n_src, dt, n_tgt, mode, dout, info);
+                    });
+}
+
+int csr_pair_distances_weighted_host(const void* indptr, const void* indices, int32_t index_width, const double* values,
+                                     uint64_t n, uint64_t nnz, const int64_t* sources, uint64_t n_src,
+                                     const int64_t* targets, uint64_t n_tgt, void* out, int32_t device,
+                                     g2n_wdist_info* info) {
+  return pairs_host("g2n_csr_pair_distances_weighted_host", indptr, indices, index_width, values, true, n, nnz, sources,
+                    n_src, targets, n_tgt, G2N_PAIR_TABLE, out, device,
+                    [&](g2n_context* c, const StagedCsr& d, const int64_t* ds, const int64_t* dt, void* dout) {
+                      wpair_distances(c, d.indptr, d.indices, index_width, d.values, n, nnz, ds, n_src, dt, n_tgt, dout,
+                                      info);
+                    });
 }
 
 // ------------------------------------------- a host build's result for a request ------
@@ -681,7 +983,7 @@ static NameTable name_table(g2n_context* c, const g2n_result& D) {
 // blob, the request's step names are looked up in it in one launch, and g2n_csr_path_distances runs
 // on the ids.
 static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, const DistRequest& q) {
-  const std::string who = "g2n_distances_from_path";
+  const std::string who = q.pairs ? "g2n_pair_distances_from_path" : "g2n_distances_from_path";
   *q.oriented = 0;
   *q.missing_step = -1;
   const bool weighted = q.winfo != nullptr;
@@ -696,8 +998,15 @@ static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
     *q.bad_weight = 1;
     return;
   }
+  // (a pair request: the source's steps are the sources, the target's the targets — g2n_pair_distances_from_path)
+  const uint64_t n_a = q.n_source_steps, n_b = q.n_steps - q.n_source_steps;
   const uint64_t cell = q.mode != G2N_DIST_MIN ? 16 : weighted ? 8 : 4;
-  check_tables(who, q.K, cell);
+  if (q.pairs) {
+    check_pair_call(who, q.mode, weighted, n_a, n_b);
+    check_pair_out(who, pair_out_bytes(q.mode, weighted, n_a, n_b));
+  } else {
+    check_tables(who, q.K, cell);
+  }
   Events<2> ev;
   ev.create();
   G2N_HIP(hipEventRecord(ev.e[0], c->stream));
@@ -735,16 +1044,23 @@ static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
     }
     return;
   }
-  const uint64_t tbytes = table_bytes(q.K, cell);
+  const uint64_t tbytes = q.pairs ? pair_out_bytes(q.mode, weighted, n_a, n_b) : table_bytes(q.K, cell);
   void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
-  if (weighted) {
+  if (q.pairs && weighted) {
+    wpair_distances(c, D.indptr, D.indices, D.index_width, (const double*)D.data, n, (uint64_t)D.nnz, dpn, n_a,
+                    dpn + n_a, n_b, dtab, q.winfo);
+  } else if (q.pairs) {
+    pair_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpn, n_a, dpn + n_a, n_b, q.mode, dtab,
+                   q.info);
+    q.info->ms_resolve = ms;
+  } else if (weighted) {
     wpath_distances(c, D.indptr, D.indices, D.index_width, (const double*)D.data, n, (uint64_t)D.nnz, dpp, dpn, q.K,
                     q.mode, dtab, q.winfo);
   } else {
     path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, q.K, q.mode, dtab, q.info);
     q.info->ms_resolve = ms;
   }
-  if (tbytes) G2N_HIP(hipMemcpyAsync(q.tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
+  if (tbytes && q.tables) G2N_HIP(hipMemcpyAsync(q.tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
 

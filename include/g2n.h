@@ -699,6 +699,55 @@ int g2n_seq_wdistance_from_path(const char *path, const g2n_options *opts, const
                                 const uint8_t *seq_b, uint64_t len_b, double *out_dist, g2n_seq_hits **hits,
                                 g2n_seq_info *info, int32_t *oriented, int32_t *bad_weight, g2n_result **res);
 
+/* ---- node-to-node distances (gfa2network/analysis.py:142-159 genome_distance(method="mean")) --------
+ * The distance from every source to every target over a CSR: what the reference takes from
+ * len(A) * len(B) calls of shortest_path_length, as ceil(n_src / 64) bit-parallel breadth-first
+ * searches (g2n_pairs.hip).  sources / targets are int64 node ids in list order, duplicates kept;
+ * -1 is no node (a source that reaches nothing, a target nothing reaches).  d(i, t) = the hops from
+ * sources[i] to targets[t], 0 when they are the same node.
+ *   G2N_PAIR_SUMS   out = S then C, n_src uint64 each: C[i] = how many target occurrences source i
+ *                   reaches, S[i] = the sum of their distances (O(n_src) output, whatever n_tgt)
+ *   G2N_PAIR_TABLE  out = D, n_src x n_tgt uint32 row-major, 0xFFFFFFFF where t is not reached
+ * info as g2n_csr_path_distances', batches = ceil(n_src / 64).  The weighted calls take float64
+ * values as g2n_csr_path_distances_weighted does (finite, >= 0) and know the table only: out = n_src x
+ * n_tgt float64, d(i, t) bit for bit Dijkstra's, +inf where not reached — a float sum's order is the
+ * caller's to choose.  info as g2n_csr_path_distances_weighted's, with sources for paths.
+ *
+ * DEVICE pointers on ctx's device; scratch from ctx's arena; returns after the stream drained.
+ * G2N_E_UNSUPPORTED for n >= 2^31 - 1, nnz >= 2^32 - 1, n_src or n_tgt >= 2^32 - 1; G2N_E_ARG for a
+ * bad indptr, an index outside [0, n) or an id outside [0, n) other than -1 — nothing out of range is
+ * ever addressed, and d_out is not written unless every array passed its check. */
+#define G2N_PAIR_SUMS 0
+#define G2N_PAIR_TABLE 1
+int g2n_csr_pair_distances(g2n_context *ctx, const void *d_indptr, const void *d_indices, int32_t index_width,
+                           uint64_t n, uint64_t nnz, const int64_t *d_sources, uint64_t n_src,
+                           const int64_t *d_targets, uint64_t n_tgt, int32_t mode, void *d_out, g2n_dist_info *info);
+int g2n_csr_pair_distances_weighted(g2n_context *ctx, const void *d_indptr, const void *d_indices, int32_t index_width,
+                                    const double *d_values, uint64_t n, uint64_t nnz, const int64_t *d_sources,
+                                    uint64_t n_src, const int64_t *d_targets, uint64_t n_tgt, void *d_out,
+                                    g2n_wdist_info *info);
+
+/* The same for arrays in HOST memory (out too): uploaded to `device` (the host entry points' cached
+ * context).  Also G2N_E_UNSUPPORTED for an output past the device's free memory. */
+int g2n_csr_pair_distances_host(const void *indptr, const void *indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                                const int64_t *sources, uint64_t n_src, const int64_t *targets, uint64_t n_tgt,
+                                int32_t mode, void *out, int32_t device, g2n_dist_info *info);
+int g2n_csr_pair_distances_weighted_host(const void *indptr, const void *indices, int32_t index_width,
+                                         const double *values, uint64_t n, uint64_t nnz, const int64_t *sources,
+                                         uint64_t n_src, const int64_t *targets, uint64_t n_tgt, void *out,
+                                         int32_t device, g2n_wdist_info *info);
+
+/* genome_distance(method="mean") of a file: built, resolved and reported as g2n_distances_from_path
+ * (source, target >= 0: two paths of `paths`), with the source's steps as the sources and the target's
+ * as the targets of g2n_csr_pair_distances — out (host) as that call's for `mode`, info filled, winfo
+ * and bad_weight may be null.  With a weight tag in opts the graph is g2n_wdistances_from_path's LAST
+ * build, mode must be G2N_PAIR_TABLE, out is the float64 table, and winfo and bad_weight are
+ * required (info may be null).  *missing_step: the first step of the source that is no node (an index
+ * into its steps; nothing is searched then), a target step that is none is a target never reached. */
+int g2n_pair_distances_from_path(const char *path, const g2n_options *opts, const g2n_paths *paths, int64_t source,
+                                 int64_t target, int32_t mode, void *out, g2n_dist_info *info, g2n_wdist_info *winfo,
+                                 int32_t *oriented, int64_t *missing_step, int32_t *bad_weight, g2n_result **res);
+
 #ifdef __cplusplus
 }
 #endif
