@@ -595,24 +595,62 @@ def stats_from_path(path: str, opts: Options) -> tuple[RawResult, dict, int]:
     return _from_result(res, rc), _stats_dict(st), int(n_paths.value)
 
 
-def csr_stats_host(indptr: np.ndarray, indices: np.ndarray, n: int, directed: bool, device: int = 0) -> dict:
-    """g2n_csr_stats_host on a host CSR's structure: indptr / indices both int32 or both int64."""
-    lib = load()
+def _csr_args(indptr: np.ndarray, indices: np.ndarray, n: int, values=None):
+    """A host CSR as the _host entry points take it: (indptr, indices, values or None — contiguous —,
+    the index dtype).  indptr / indices both int32 or both int64 (n + 1 offsets), values float64, one
+    per index."""
     idt = np.dtype(indptr.dtype)
     if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
         raise TypeError("indptr / indices must both be int32 or both int64")
+    if values is not None and np.dtype(values.dtype) != np.dtype(np.float64):
+        raise TypeError("values must be float64")
     ip, ix = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
+    val = None if values is None else np.ascontiguousarray(values)
     if len(ip) != n + 1:
         raise ValueError("indptr must hold n + 1 offsets")
-    st = GraphStats()
-    rc = lib.g2n_csr_stats_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, n, len(ix),
-                                int(bool(directed)), int(device), ctypes.byref(st))
+    if val is not None and len(val) != len(ix):
+        raise ValueError("values must hold one value per index")
+    return ip, ix, val, idt
+
+
+def _ptr(a: np.ndarray):
+    """The array's address, None for an empty one."""
+    return a.ctypes.data if a.size else None
+
+
+def _raise_status(rc: int, what: str) -> None:
+    """A _host entry point's status as an exception (``what`` names the query); OK returns."""
     if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
-        raise NotImplementedError(f"GPU graph statistics: {last_error()}")
+        raise NotImplementedError(f"GPU {what}: {last_error()}")
     if rc == E_ARG:
-        raise ValueError(f"GPU graph statistics: {last_error()}")
+        raise ValueError(f"GPU {what}: {last_error()}")
     if rc != OK:
         raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+
+
+def _path_args(path_ptr, path_nodes):
+    """K paths as (int64 path_ptr of K + 1 offsets, int64 path_nodes, K)."""
+    pp = np.ascontiguousarray(path_ptr, dtype=np.int64)
+    pn = np.ascontiguousarray(path_nodes, dtype=np.int64)
+    K = len(pp) - 1
+    if K < 0 or pp[0] != 0 or pp[K] != len(pn):
+        raise ValueError("path_ptr must hold K + 1 offsets from 0 to len(path_nodes)")
+    return pp, pn, K
+
+
+def _dist_info(info: DistInfo) -> dict:
+    return {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
+            "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
+
+
+def csr_stats_host(indptr: np.ndarray, indices: np.ndarray, n: int, directed: bool, device: int = 0) -> dict:
+    """g2n_csr_stats_host on a host CSR's structure: indptr / indices both int32 or both int64."""
+    lib = load()
+    ip, ix, _val, idt = _csr_args(indptr, indices, n)
+    st = GraphStats()
+    rc = lib.g2n_csr_stats_host(ip.ctypes.data, _ptr(ix), idt.itemsize, n, len(ix), int(bool(directed)), int(device),
+                                ctypes.byref(st))
+    _raise_status(rc, "graph statistics")
     return _stats_dict(st)
 
 
@@ -623,31 +661,14 @@ def csr_path_distances_host(indptr: np.ndarray, indices: np.ndarray, n: int, pat
     g2n_dist_info fields) — the directed K x K tables, uint32 D (0xFFFFFFFF = unreached) or uint64
     S and C."""
     lib = load()
-    idt = np.dtype(indptr.dtype)
-    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
-        raise TypeError("indptr / indices must both be int32 or both int64")
-    ip, ix = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
-    pp = np.ascontiguousarray(path_ptr, dtype=np.int64)
-    pn = np.ascontiguousarray(path_nodes, dtype=np.int64)
-    if len(ip) != n + 1:
-        raise ValueError("indptr must hold n + 1 offsets")
-    K = len(pp) - 1
-    if K < 0 or pp[0] != 0 or pp[K] != len(pn):
-        raise ValueError("path_ptr must hold K + 1 offsets from 0 to len(path_nodes)")
+    ip, ix, _val, idt = _csr_args(indptr, indices, n)
+    pp, pn, K = _path_args(path_ptr, path_nodes)
     out = np.empty((2, K, K), dtype=np.uint64) if mean else np.empty((1, K, K), dtype=np.uint32)
     info = DistInfo()
-    rc = lib.g2n_csr_path_distances_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, n, len(ix),
-                                         pp.ctypes.data, pn.ctypes.data if pn.size else None, K,
-                                         DIST_MEAN if mean else DIST_MIN, out.ctypes.data if out.size else None,
-                                         int(device), ctypes.byref(info))
-    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
-        raise NotImplementedError(f"GPU path distances: {last_error()}")
-    if rc == E_ARG:
-        raise ValueError(f"GPU path distances: {last_error()}")
-    if rc != OK:
-        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
-    return tuple(out), {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
-                        "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
+    rc = lib.g2n_csr_path_distances_host(ip.ctypes.data, _ptr(ix), idt.itemsize, n, len(ix), pp.ctypes.data, _ptr(pn), K,
+                                         DIST_MEAN if mean else DIST_MIN, _ptr(out), int(device), ctypes.byref(info))
+    _raise_status(rc, "path distances")
+    return tuple(out), _dist_info(info)
 
 
 def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, values: np.ndarray, n: int,
@@ -658,45 +679,19 @@ def csr_path_distances_weighted_host(indptr: np.ndarray, indices: np.ndarray, va
     fields) — the directed K x K tables, float64 D (inf = unreached) or float64 S and uint64 C.
     ``mean="fold"``: G2N_DIST_MEAN_FOLD, S above the diagonal holding the reference's running total."""
     lib = load()
-    idt = np.dtype(indptr.dtype)
-    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
-        raise TypeError("indptr / indices must both be int32 or both int64")
-    if np.dtype(values.dtype) != np.dtype(np.float64):
-        raise TypeError("values must be float64")
-    ip, ix, val = np.ascontiguousarray(indptr), np.ascontiguousarray(indices), np.ascontiguousarray(values)
-    pp = np.ascontiguousarray(path_ptr, dtype=np.int64)
-    pn = np.ascontiguousarray(path_nodes, dtype=np.int64)
-    if len(ip) != n + 1:
-        raise ValueError("indptr must hold n + 1 offsets")
-    if len(val) != len(ix):
-        raise ValueError("values must hold one value per index")
-    K = len(pp) - 1
-    if K < 0 or pp[0] != 0 or pp[K] != len(pn):
-        raise ValueError("path_ptr must hold K + 1 offsets from 0 to len(path_nodes)")
+    ip, ix, val, idt = _csr_args(indptr, indices, n, values)
+    pp, pn, K = _path_args(path_ptr, path_nodes)
     out = np.empty((2 if mean else 1, K, K), dtype=np.float64)
     info = WDistInfo()
-    rc = lib.g2n_csr_path_distances_weighted_host(ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize,
-                                                  val.ctypes.data if val.size else None, n, len(ix), pp.ctypes.data,
-                                                  pn.ctypes.data if pn.size else None, K,
-                                                  _wdist_mode(mean),
-                                                  out.ctypes.data if out.size else None, int(device),
+    rc = lib.g2n_csr_path_distances_weighted_host(ip.ctypes.data, _ptr(ix), idt.itemsize, _ptr(val), n, len(ix),
+                                                  pp.ctypes.data, _ptr(pn), K, _wdist_mode(mean), _ptr(out), int(device),
                                                   ctypes.byref(info))
-    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
-        raise NotImplementedError(f"GPU weighted path distances: {last_error()}")
-    if rc == E_ARG:
-        raise ValueError(f"GPU weighted path distances: {last_error()}")
-    if rc != OK:
-        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+    _raise_status(rc, "weighted path distances")
     tabs = (out[0], out[1].view(np.uint64)) if mean else (out[0],)
     return tabs, _wdist_info(info)
 
 
 PAIR_SUMS, PAIR_TABLE = 0, 1
-
-
-def _dist_info(info: DistInfo) -> dict:
-    return {"levels": int(info.levels), "launches": int(info.launches), "batches": int(info.batches),
-            "ms_resolve": float(info.ms_resolve), "ms_bfs": float(info.ms_bfs)}
 
 
 def csr_pair_distances_host(indptr: np.ndarray, indices: np.ndarray, values, n: int, sources: np.ndarray,
@@ -707,42 +702,26 @@ def csr_pair_distances_host(indptr: np.ndarray, indices: np.ndarray, values, n: 
     len(sources) x len(targets), uint32 (0xFFFFFFFF = unreached) or float64 (inf).  info: the
     g2n_dist_info fields, or g2n_wdist_info's with values."""
     lib = load()
-    idt = np.dtype(indptr.dtype)
-    if idt not in (np.dtype(np.int32), np.dtype(np.int64)) or np.dtype(indices.dtype) != idt:
-        raise TypeError("indptr / indices must both be int32 or both int64")
-    ip, ix = np.ascontiguousarray(indptr), np.ascontiguousarray(indices)
-    if len(ip) != n + 1:
-        raise ValueError("indptr must hold n + 1 offsets")
+    ip, ix, _val, idt = _csr_args(indptr, indices, n)  # (the values' checks come after the lists' and the mode's)
     src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
     tgt = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
     weighted = values is not None
     if weighted:
         if not table:
             raise ValueError("the weighted pair distances are a table (a float sum's order is the caller's)")
-        if np.dtype(values.dtype) != np.dtype(np.float64):
-            raise TypeError("values must be float64")
-        val = np.ascontiguousarray(values)
-        if len(val) != len(ix):
-            raise ValueError("values must hold one value per index")
+        val = _csr_args(ip, ix, n, values)[2]
         out = np.empty((len(src), len(tgt)), dtype=np.float64)
         info = WDistInfo()
-        rc = lib.g2n_csr_pair_distances_weighted_host(
-            ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, val.ctypes.data if val.size else None, n,
-            len(ix), src.ctypes.data if src.size else None, len(src), tgt.ctypes.data if tgt.size else None, len(tgt),
-            out.ctypes.data if out.size else None, int(device), ctypes.byref(info))
+        rc = lib.g2n_csr_pair_distances_weighted_host(ip.ctypes.data, _ptr(ix), idt.itemsize, _ptr(val), n, len(ix),
+                                                      _ptr(src), len(src), _ptr(tgt), len(tgt), _ptr(out), int(device),
+                                                      ctypes.byref(info))
     else:
         out = np.empty((len(src), len(tgt)), dtype=np.uint32) if table else np.empty((2, len(src)), dtype=np.uint64)
         info = DistInfo()
-        rc = lib.g2n_csr_pair_distances_host(
-            ip.ctypes.data, ix.ctypes.data if ix.size else None, idt.itemsize, n, len(ix),
-            src.ctypes.data if src.size else None, len(src), tgt.ctypes.data if tgt.size else None, len(tgt),
-            PAIR_TABLE if table else PAIR_SUMS, out.ctypes.data if out.size else None, int(device), ctypes.byref(info))
-    if rc == E_UNSUPPORTED:  # a documented size limit (include/g2n.h)
-        raise NotImplementedError(f"GPU pair distances: {last_error()}")
-    if rc == E_ARG:
-        raise ValueError(f"GPU pair distances: {last_error()}")
-    if rc != OK:
-        raise RuntimeError(f"{status_name(rc)}: {last_error()}")
+        rc = lib.g2n_csr_pair_distances_host(ip.ctypes.data, _ptr(ix), idt.itemsize, n, len(ix), _ptr(src), len(src),
+                                             _ptr(tgt), len(tgt), PAIR_TABLE if table else PAIR_SUMS, _ptr(out),
+                                             int(device), ctypes.byref(info))
+    _raise_status(rc, "pair distances")
     return ((out,) if table else (out[0], out[1])), (_wdist_info(info) if weighted else _dist_info(info))
 
 

@@ -856,18 +856,26 @@ def _path_arrays(paths):
     return ptr, np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
 
 
-def _weighted_path_distances(A, paths, method, device, return_info):
-    A, data = _weighted_csr(A)
+def _distance_csr(A, who: str, weighted: bool, what: str = "path"):
+    """``A`` as the distance functions take it: (indptr, indices, float64 data or None, n).  ``who`` is
+    the function the messages name, ``what`` the distances the size limit's message names."""
+    if not sp.issparse(A):
+        raise TypeError(f"{who} takes a scipy sparse matrix")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"{who} takes a square matrix")
+    data = None
+    if weighted:
+        A, data = _weighted_csr(A)
+    elif A.format != "csr":
+        # structure only: unit values in a dtype whose sums cannot overflow
+        C = A.tocoo()
+        A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
+        A.sum_duplicates()
     n = int(A.shape[0])
     if n >= 2**31 - 1:
-        raise NotImplementedError("GPU path distances need node ids below 2^31 - 1")
-    ptr, nodes = _path_arrays(paths)
+        raise NotImplementedError(f"GPU {what} distances need node ids below 2^31 - 1")
     idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
-    mean = method != "min"
-    tabs, info = nat.csr_path_distances_weighted_host(np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt),
-                                                      data, n, ptr, nodes, mean, device)
-    M = weighted_mean_table(*tabs) if mean else weighted_min_table(tabs[0])
-    return (M, info) if return_info else M
+    return np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt), data, n
 
 
 def path_distances(A, paths, *, method: str = "min", weighted: bool = False, device: int = 0,
@@ -892,51 +900,16 @@ def path_distances(A, paths, *, method: str = "min", weighted: bool = False, dev
     returns its symmetric mean.  Runs on the GPU as a bit-parallel breadth-first search, 64 paths at
     a time (g2n_csr_path_distances_host); a matrix in another format is converted first.
     ``return_info=True`` also returns the g2n_dist_info fields (levels, launches, batches, ms_*)."""
-    if not sp.issparse(A):
-        raise TypeError("path_distances takes a scipy sparse matrix")
-    if A.shape[0] != A.shape[1]:
-        raise ValueError("path_distances takes a square matrix")
-    if weighted:
-        return _weighted_path_distances(A, paths, method, device, return_info)
-    if A.format != "csr":
-        # structure only: unit values in a dtype whose sums cannot overflow
-        C = A.tocoo()
-        A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
-        A.sum_duplicates()
-    n = int(A.shape[0])
-    if n >= 2**31 - 1:
-        raise NotImplementedError("GPU path distances need node ids below 2^31 - 1")
-    lists = [np.asarray(p, dtype=np.int64).reshape(-1) for p in paths]
-    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
-    np.cumsum([len(p) for p in lists], out=ptr[1:])
-    nodes = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
-    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
+    ip, ix, data, n = _distance_csr(A, "path_distances", weighted)
+    ptr, nodes = _path_arrays(paths)
     mean = method != "min"
-    tabs, info = nat.csr_path_distances_host(np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt), n, ptr,
-                                             nodes, mean, device)
-    M = mean_table(*tabs) if mean else min_table(tabs[0])
-    return (M, info) if return_info else M
-
-
-def _pair_csr(A, who: str, weighted: bool):
-    """``A`` as ``path_distances`` takes it: (indptr, indices, float64 data or None, n)."""
-    if not sp.issparse(A):
-        raise TypeError(f"{who} takes a scipy sparse matrix")
-    if A.shape[0] != A.shape[1]:
-        raise ValueError(f"{who} takes a square matrix")
-    data = None
     if weighted:
-        A, data = _weighted_csr(A)
-    elif A.format != "csr":
-        # structure only: unit values in a dtype whose sums cannot overflow
-        C = A.tocoo()
-        A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
-        A.sum_duplicates()
-    n = int(A.shape[0])
-    if n >= 2**31 - 1:
-        raise NotImplementedError("GPU pair distances need node ids below 2^31 - 1")
-    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
-    return np.asarray(A.indptr, dtype=idt), np.asarray(A.indices, dtype=idt), data, n
+        tabs, info = nat.csr_path_distances_weighted_host(ip, ix, data, n, ptr, nodes, mean, device)
+        M = weighted_mean_table(*tabs) if mean else weighted_min_table(tabs[0])
+    else:
+        tabs, info = nat.csr_path_distances_host(ip, ix, n, ptr, nodes, mean, device)
+        M = mean_table(*tabs) if mean else min_table(tabs[0])
+    return (M, info) if return_info else M
 
 
 def node_distances(A, sources, targets, *, weighted: bool = False, device: int = 0, return_info: bool = False):
@@ -948,7 +921,7 @@ def node_distances(A, sources, targets, *, weighted: bool = False, device: int =
     ``-1`` is no node (a row or column of ``inf``), any other id outside ``[0, n)`` raises ValueError.
     One bit-parallel search carries 64 sources (g2n_csr_pair_distances_host, g2n_pairs.hip).
     ``return_info=True`` also returns the g2n_dist_info (weighted: g2n_wdist_info) fields."""
-    ip, ix, data, n = _pair_csr(A, "node_distances", weighted)
+    ip, ix, data, n = _distance_csr(A, "node_distances", weighted, "pair")
     (D,), info = nat.csr_pair_distances_host(ip, ix, data, n, sources, targets, True, device)
     if not weighted:
         M = D.astype(np.float64)
@@ -963,7 +936,7 @@ def pair_sums(A, sources, targets, *, device: int = 0, return_info: bool = False
     distances — the row sums of ``node_distances`` over its finite cells, without the table: the
     accumulators are O(len(sources)) whatever ``len(targets)`` (extension; G2N_PAIR_SUMS).  Lists as
     ``node_distances`` takes them."""
-    ip, ix, _data, n = _pair_csr(A, "pair_sums", False)
+    ip, ix, _data, n = _distance_csr(A, "pair_sums", False, "pair")
     (S, C), info = nat.csr_pair_distances_host(ip, ix, None, n, sources, targets, False, device)
     return (S, C, info) if return_info else (S, C)
 

@@ -86,14 +86,17 @@ static uint64_t table_bytes(uint64_t K, uint64_t cell) {
   return K * K * cell;
 }
 
-// the K x K tables of one call (and the batch's K done words) must fit the device's free memory
-static void check_tables(const std::string& who, uint64_t K, uint64_t cell) {
+// an output this library allocates (bytes; ~0 = past 2^63) must fit the device's free memory
+static void check_fits(const std::string& who, uint64_t bytes, const std::string& what) {
   size_t f = 0, t = 0;
   G2N_HIP(hipMemGetInfo(&f, &t));
+  if (bytes > f) throw Failure(G2N_E_UNSUPPORTED, who + ": " + what + " the device's free memory");
+}
+
+// the K x K tables of one call (and the batch's K done words)
+static void check_tables(const std::string& who, uint64_t K, uint64_t cell) {
   const uint64_t want = table_bytes(K, cell);
-  if ((K && !want) || want + K * 8 > f)
-    throw Failure(G2N_E_UNSUPPORTED,
-                  who + ": the K x K tables of " + std::to_string(K) + " paths exceed the device's free memory");
+  check_fits(who, K && !want ? ~0ull : want + K * 8, "the K x K tables of " + std::to_string(K) + " paths exceed");
 }
 
 // a _host entry point's call on the shared context of `device`: lock, open the call, f(c), trim
@@ -201,28 +204,36 @@ int csr_stats_host(const void* indptr, const void* indices, int32_t index_width,
   });
 }
 
-// ------------------------------------------- path distances: what both searches share ------
-// The caller's arrays, checked whole on the device before anything is searched (values: null for
-// hops); the steps' paths into step_path and the nodes' step counts into cnt (n + 1, cleared here).
-template <class I>
+// ------------------------------------------- distances: what the searches share ------
+// The caller's arrays, checked whole on the device before anything is searched or written (values:
+// null for hops): the CSR here, the caller's lists — `what` in the message — by the launches of lists(st).
+template <class I, class Lists>
 static void check_on_device(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
-                            const double* values, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
-                            const int64_t* path_nodes, uint64_t K, uint64_t steps, uint32_t* step_path, uint32_t* cnt,
-                            DistState* st) {
+                            const double* values, uint64_t n, uint64_t nnz, DistState* st, const char* what,
+                            Lists&& lists) {
   const unsigned gcap = (unsigned)c->n_cu * 8;
   G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-  G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
   hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
                      indices, n, nnz, st);
   if (values && nnz)
     hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for(nnz), gcap)), dim3(256), 0, c->stream, values, nnz, st);
-  hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
-  if (steps)
-    hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
-                       step_path, cnt, st);
+  lists(st);
   if (read_dev(c, st).bad)
-    throw Failure(G2N_E_ARG, who + ": indptr / indices / path_ptr / path_nodes out of range" +
+    throw Failure(G2N_E_ARG, who + ": indptr / indices / " + what + " out of range" +
                                  (values ? ", or a value that is negative or not finite" : ""));
+}
+
+// check_on_device's lists of a path search: the steps' paths into step_path and the nodes' step counts
+// into cnt (n + 1, cleared here)
+static auto path_lists(g2n_context* c, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K, uint64_t steps,
+                       uint64_t n, uint32_t* step_path, uint32_t* cnt) {
+  return [=](DistState* st) {
+    G2N_HIP(hipMemsetAsync(cnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_dist_paths_check, dim3(grid_for(K)), dim3(256), 0, c->stream, path_ptr, K, steps, st);
+    if (steps)
+      hipLaunchKernelGGL(k_dist_steps, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_ptr, path_nodes, K, steps, n,
+                         step_path, cnt, st);
+  };
 }
 
 // One batch's search from the sources already in next (any: there are some), level by level — a
@@ -272,6 +283,86 @@ static uint32_t run_frontier(g2n_context* c, const std::string& who, DistState* 
   return h.last_level;
 }
 
+// what one search's frontier works in (the arena's S_D* slots); a weighted search has its distances beside it
+struct SearchBufs {
+  DistState* st;
+  unsigned long long* next;
+  uint32_t* queue;
+  unsigned long long* qmask;
+  uint32_t* long_rows;
+  uint64_t long_cap;
+};
+
+static SearchBufs search_bufs(g2n_context* c, uint64_t n, uint64_t nnz) {
+  SearchBufs w{};
+  w.st = dget<DistState>(c, S_DSTATE, 1);
+  w.next = dget<unsigned long long>(c, S_DNEXT, n);
+  w.queue = dget<uint32_t>(c, S_DQUEUE, n);
+  w.qmask = dget<unsigned long long>(c, S_DQMASK, n);
+  w.long_cap = nnz / kStatsShortRow + 1;
+  w.long_rows = dget<uint32_t>(c, S_DLONG, w.long_cap);
+  return w;
+}
+
+// --------------------------------------------------------- hop searches ------
+// what one hop search works in: the seen bits, then what every search does
+struct HopBufs : SearchBufs {
+  unsigned long long* seen;
+};
+
+static HopBufs hop_bufs(g2n_context* c, uint64_t n, uint64_t nnz) {
+  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
+  return {search_bufs(c, n, nnz), seen};
+}
+
+// n_batches batches of 64 hop searches each.  Per batch seen, next and the state are cleared; seed(k)
+// sets batch k's sources in seen / next and returns whether it launched (false: the batch has none);
+// collect(L) and narrow(budget) are run_frontier's, over the caller's accumulators.
+template <class I, class Seed, class Collect, class Narrow>
+static void hop_batches(g2n_context* c, const std::string& who, const I* indptr, const I* indices, uint64_t n,
+                        uint64_t nnz, const HopBufs& b, uint64_t n_batches, g2n_dist_info* info, Seed&& seed,
+                        Collect&& collect, Narrow&& narrow) {
+  const unsigned gcap = (unsigned)c->n_cu * 8;
+  int64_t launches = 0, levels = 0;
+  for (uint64_t k = 0; k < n_batches; k++) {
+    G2N_HIP(hipMemsetAsync(b.seen, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(b.next, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(b.st, 0, sizeof(DistState), c->stream));
+    const bool any = seed(k);
+    launches += any;
+    const uint32_t last = run_frontier(
+        c, who, b.st, n, any, &launches, collect,
+        [&](uint32_t count) {
+          hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
+                             indices, n, nnz, b.seen, b.next, (const uint32_t*)b.queue, (const unsigned long long*)b.qmask,
+                             b.long_rows, b.long_cap, b.st);
+          hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
+                             nnz, b.seen, b.next, (const uint32_t*)b.queue, (const unsigned long long*)b.qmask,
+                             (const uint32_t*)b.long_rows, b.long_cap, b.st);
+        },
+        narrow);
+    levels = std::max<int64_t>(levels, last);
+  }
+  info->levels = levels;
+  info->launches = launches;
+  info->batches = (int64_t)n_batches;
+}
+
+// A hop search's timed shell: search(indptr, indices) in the CSR's index type, its stream time into ms_bfs
+template <class Search>
+static void timed_hop_search(g2n_context* c, int32_t index_width, const void* indptr, const void* indices,
+                             g2n_dist_info* info, Search&& search) {
+  Events<2> ev;
+  ev.create();
+  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
+  with_index_type(index_width, indptr, indices, search);
+  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  info->ms_bfs = ms;
+}
+
 // --------------------------------------------------------- path distances ------
 // g2n_csr_path_distances on c's stream (the caller holds c's lock and opened the call); tables: device.
 template <class I>
@@ -280,14 +371,13 @@ static void path_distances_t(g2n_context* c, const I* indptr, const I* indices, 
                              void* tables, g2n_dist_info* info) {
   const std::string who = "g2n_csr_path_distances";
   auto* st = dget<DistState>(c, S_DSTATE, 1);
-  const unsigned gcap = (unsigned)c->n_cu * 8;
   auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
   auto* mem_ptr = dget<uint32_t>(c, S_DMPTR, n + 1);
   auto* cursor = dget<uint32_t>(c, S_DCUR, n + 1);
   auto* mem_path = dget<uint32_t>(c, S_DMPATH, steps);
   auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
-  check_on_device(c, who, indptr, indices, (const double*)nullptr, n, nnz, path_ptr, path_nodes, K, steps, step_path,
-                  cnt, st);
+  check_on_device(c, who, indptr, indices, (const double*)nullptr, n, nnz, st, "path_ptr / path_nodes",
+                  path_lists(c, path_ptr, path_nodes, K, steps, n, step_path, cnt));
   // ---- membership: the steps sorted by node
   scan_excl<uint32_t, uint32_t>(c, cnt, mem_ptr, n + 1);
   G2N_HIP(hipMemcpyAsync(cursor, mem_ptr, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
@@ -305,51 +395,30 @@ static void path_distances_t(g2n_context* c, const I* indptr, const I* indices, 
     acc.done = dget<unsigned long long>(c, S_DDONE, K);
     G2N_HIP(hipMemsetAsync(tables, 0xFF, K * K * 4, c->stream));
   }
-  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
-  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
-  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
-  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
-  const uint64_t long_cap = nnz / kStatsShortRow + 1;
-  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
+  const HopBufs b = hop_bufs(c, n, nnz);
   std::vector<int64_t> h_ptr(K + 1);
   G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   G2N_HIP(hipStreamSynchronize(c->stream));
-  const unsigned gn = std::min(grid_for(n), gcap);
-  int64_t launches = 0, levels = 0, batches = 0;
-  for (uint64_t base = 0; base < K; base += 64, batches++) {
-    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[std::min<uint64_t>(base + 64, K)];
-    acc.base = (uint32_t)base;
-    G2N_HIP(hipMemsetAsync(seen, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
-    if (acc.done) G2N_HIP(hipMemsetAsync(acc.done, 0, K * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-    if (s1 > s0) {
-      hipLaunchKernelGGL(k_dist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
-                         (const uint32_t*)step_path, (uint32_t)base, seen, next);
-      launches++;
-    }
-    const uint32_t last = run_frontier(
-        c, who, st, n, s1 > s0, &launches,
-        [&](uint32_t L) {
-          hipLaunchKernelGGL(k_dist_collect, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc, st);
-        },
-        [&](uint32_t count) {
-          hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
-                             indices, n, nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
-                             long_rows, long_cap, st);
-          hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
-                             nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
-                             (const uint32_t*)long_rows, long_cap, st);
-        },
-        [&](uint32_t budget) {
-          hipLaunchKernelGGL(k_dist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n, nnz, seen,
-                             next, queue, qmask, acc, st, budget);
-        });
-    levels = std::max<int64_t>(levels, last);
-  }
-  info->levels = levels;
-  info->launches = launches;
-  info->batches = batches;
+  const unsigned gn = std::min(grid_for(n), (unsigned)c->n_cu * 8);
+  hop_batches(
+      c, who, indptr, indices, n, nnz, b, (K + 63) / 64, info,
+      [&](uint64_t k) {
+        const uint64_t base = k * 64;
+        const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[std::min<uint64_t>(base + 64, K)];
+        acc.base = (uint32_t)base;
+        if (acc.done) G2N_HIP(hipMemsetAsync(acc.done, 0, K * 8, c->stream));
+        if (s1 > s0)
+          hipLaunchKernelGGL(k_dist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
+                             (const uint32_t*)step_path, (uint32_t)base, b.seen, b.next);
+        return s1 > s0;
+      },
+      [&](uint32_t L) {
+        hipLaunchKernelGGL(k_dist_collect, dim3(gn), dim3(256), 0, c->stream, b.next, n, L, b.queue, b.qmask, acc, b.st);
+      },
+      [&](uint32_t budget) {
+        hipLaunchKernelGGL(k_dist_narrow<I>, dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n, nnz, b.seen,
+                           b.next, b.queue, b.qmask, acc, b.st, budget);
+      });
 }
 
 static void path_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
@@ -361,41 +430,12 @@ static void path_distances(g2n_context* c, const void* indptr, const void* indic
   check_csr(who, index_width, n, nnz, !K || (path_ptr && tables && (!n || indptr)), !K || indices, K != 0);
   if (K == 0) return;
   const uint64_t steps = path_steps_dev(c, who, path_ptr, K, path_nodes);
-  Events<2> ev;
-  ev.create();
-  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
-  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
+  timed_hop_search(c, index_width, indptr, indices, info, [&](auto* ip, auto* ix) {
     path_distances_t(c, ip, ix, n, nnz, path_ptr, path_nodes, K, steps, mode == G2N_DIST_MEAN, tables, info);
   });
-  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  info->ms_bfs = ms;
 }
 
 // ------------------------------------------------ weighted path distances ------
-// what one weighted search works in, beside its distances (the arena's S_D* slots)
-struct WSearchBufs {
-  DistState* st;
-  unsigned long long* next;
-  uint32_t* queue;
-  unsigned long long* qmask;
-  uint32_t* long_rows;
-  uint64_t long_cap;
-};
-
-static WSearchBufs wsearch_bufs(g2n_context* c, uint64_t n, uint64_t nnz) {
-  WSearchBufs w{};
-  w.st = dget<DistState>(c, S_DSTATE, 1);
-  w.next = dget<unsigned long long>(c, S_DNEXT, n);
-  w.queue = dget<uint32_t>(c, S_DQUEUE, n);
-  w.qmask = dget<unsigned long long>(c, S_DQMASK, n);
-  w.long_cap = nnz / kStatsShortRow + 1;
-  w.long_rows = dget<uint32_t>(c, S_DLONG, w.long_cap);
-  return w;
-}
-
 // B searches a batch, of K wanted: B * n distances must fit what is free (and what the slot already holds)
 static uint64_t wdist_batch_width(g2n_context* c, const std::string& who, uint64_t n, uint64_t K) {
   uint64_t B = std::min<uint64_t>(64, K);
@@ -417,7 +457,7 @@ static uint64_t wdist_batch_width(g2n_context* c, const std::string& who, uint64
 template <class I>
 static uint32_t wdist_search(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
                              const double* values, uint64_t n, uint64_t nnz, uint64_t B, unsigned long long* dist,
-                             const WSearchBufs& w, bool any, int64_t* launches) {
+                             const SearchBufs& w, bool any, int64_t* launches) {
   const unsigned gcap = (unsigned)c->n_cu * 8;
   const unsigned gn = std::min(grid_for(n), gcap);
   return run_frontier(
@@ -439,72 +479,35 @@ static uint32_t wdist_search(g2n_context* c, const std::string& who, const I* in
       });
 }
 
-// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
-// tables: device.  Nothing is written to the tables before every array has passed its check.
-template <class I>
-static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
-                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
-                              uint64_t steps, int32_t mode, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
-  const std::string who = "g2n_csr_path_distances_weighted";
-  const bool mean = mode != G2N_DIST_MIN, fold = mode == G2N_DIST_MEAN_FOLD;
-  const WSearchBufs w = wsearch_bufs(c, n, nnz);
-  DistState* st = w.st;
-  unsigned long long* next = w.next;
-  G2N_HIP(hipEventRecord(ev[0], c->stream));
+// The K searches of one weighted call, B a batch (dist: n * B), batch k from search base(k) on.  Per
+// batch dist is filled with inf and next and the state cleared; seed(base, nb) sets the nb searches'
+// sources in dist / next and returns whether it launched (false: the batch has none); after the search
+// tables(base, nb) launches the batch's part of the caller's tables and returns its launches.  ev: three
+// events, ev[0] recorded by the caller before its checks — the first batch's search time holds them.
+template <class I, class Base, class Seed, class Tables>
+static void wdist_batches(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
+                          const double* values, uint64_t n, uint64_t nnz, uint64_t K, uint64_t B,
+                          unsigned long long* dist, const SearchBufs& w, g2n_wdist_info* info, hipEvent_t* ev,
+                          Base&& base_of, Seed&& seed, Tables&& tables) {
   const unsigned gcap = (unsigned)c->n_cu * 8;
-  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
-  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
-  check_on_device(c, who, indptr, indices, values, n, nnz, path_ptr, path_nodes, K, steps, step_path, cnt, st);
-  // ---- B paths a batch
-  const uint64_t B = wdist_batch_width(c, who, n, K);
-  auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
-  info->batch_paths = (int64_t)B;
-  // ---- tables
-  auto* D = (unsigned long long*)tables;
-  if (!mean)
-    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(K * K), gcap)), dim3(256), 0, c->stream, D, K * K,
-                       kWDistInf);
-  std::vector<int64_t> h_ptr(K + 1);
-  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  int64_t launches = 0, rounds = 0, batches = 0;
-  double ms_search = 0.0, ms_tables = 0.0;
   const uint64_t n_batches = (K + B - 1) / B;
-  for (uint64_t k = 0; k < n_batches; k++, batches++) {
-    // (mean-fold: from the last batch to the first — a row's seeds are the rows below it, k_wdist_mean_fold)
-    const uint64_t base = (fold ? n_batches - 1 - k : k) * B;
+  int64_t launches = 0, rounds = 0;
+  double ms_search = 0.0, ms_tables = 0.0;
+  for (uint64_t k = 0; k < n_batches; k++) {
+    const uint64_t base = base_of(k);
     const uint64_t nb = std::min<uint64_t>(B, K - base);
-    const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[base + nb];
-    if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
+    if (k) G2N_HIP(hipEventRecord(ev[0], c->stream));
     hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(n * B), gcap)), dim3(256), 0, c->stream, dist, n * B,
                        kWDistInf);
-    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
+    G2N_HIP(hipMemsetAsync(w.next, 0, n * 8, c->stream));
+    G2N_HIP(hipMemsetAsync(w.st, 0, sizeof(DistState), c->stream));
     launches++;
-    if (s1 > s0) {
-      hipLaunchKernelGGL(k_wdist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
-                         (const uint32_t*)step_path, (uint32_t)base, (uint32_t)B, dist, next);
-      launches++;
-    }
-    const uint32_t last = wdist_search(c, who, indptr, indices, values, n, nnz, B, dist, w, s1 > s0, &launches);
+    const bool any = seed(base, nb);
+    launches += any;
+    const uint32_t last = wdist_search(c, who, indptr, indices, values, n, nnz, B, dist, w, any, &launches);
     rounds = std::max<int64_t>(rounds, last);
-    // ---- the batch's rows of the tables
     G2N_HIP(hipEventRecord(ev[1], c->stream));
-    if (mean) {
-      hipLaunchKernelGGL(k_wdist_mean, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes, steps, n,
-                         K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base, (double*)tables,
-                         D + K * K);
-      if (fold) {
-        hipLaunchKernelGGL(k_wdist_mean_fold, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes,
-                           steps, n, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base,
-                           (double*)tables);
-        launches++;
-      }
-    } else if (steps)
-      hipLaunchKernelGGL(k_wdist_min, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
-                         (const uint32_t*)step_path, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb,
-                         (uint32_t)base, D);
-    launches++;
+    launches += tables(base, nb);
     G2N_HIP(hipEventRecord(ev[2], c->stream));
     G2N_HIP(hipEventSynchronize(ev[2]));
     float ms = 0.f;
@@ -515,9 +518,75 @@ static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices,
   }
   info->rounds = rounds;
   info->launches = launches;
-  info->batches = batches;
+  info->batches = (int64_t)n_batches;
   info->ms_search = ms_search;
   info->ms_tables = ms_tables;
+}
+
+// A weighted search's shell: search(indptr, indices, ev) in the CSR's index type, ev the three events
+// of wdist_batches
+template <class Search>
+static void weighted_search(g2n_context* c, int32_t index_width, const void* indptr, const void* indices,
+                            Search&& search) {
+  Events<3> ev;
+  ev.create();
+  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) { search(ip, ix, ev.e); });
+  G2N_HIP(hipStreamSynchronize(c->stream));
+}
+
+// g2n_csr_path_distances_weighted on c's stream (the caller holds c's lock and opened the call);
+// tables: device.  Nothing is written to the tables before every array has passed its check.
+template <class I>
+static void wpath_distances_t(g2n_context* c, const I* indptr, const I* indices, const double* values, uint64_t n,
+                              uint64_t nnz, const int64_t* path_ptr, const int64_t* path_nodes, uint64_t K,
+                              uint64_t steps, int32_t mode, void* tables, g2n_wdist_info* info, hipEvent_t* ev) {
+  const std::string who = "g2n_csr_path_distances_weighted";
+  const bool mean = mode != G2N_DIST_MIN, fold = mode == G2N_DIST_MEAN_FOLD;
+  const SearchBufs w = search_bufs(c, n, nnz);
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  auto* cnt = dget<uint32_t>(c, S_DCNT, n + 1);
+  auto* step_path = dget<uint32_t>(c, S_DSPATH, steps);
+  check_on_device(c, who, indptr, indices, values, n, nnz, w.st, "path_ptr / path_nodes",
+                  path_lists(c, path_ptr, path_nodes, K, steps, n, step_path, cnt));
+  // ---- B paths a batch
+  const uint64_t B = wdist_batch_width(c, who, n, K);
+  auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
+  info->batch_paths = (int64_t)B;
+  // ---- tables
+  auto* D = (unsigned long long*)tables;
+  if (!mean)
+    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(K * K), (unsigned)c->n_cu * 8)), dim3(256), 0, c->stream, D,
+                       K * K, kWDistInf);
+  std::vector<int64_t> h_ptr(K + 1);
+  G2N_HIP(hipMemcpyAsync(h_ptr.data(), path_ptr, (K + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  const uint64_t n_batches = (K + B - 1) / B;
+  wdist_batches(
+      c, who, indptr, indices, values, n, nnz, K, B, dist, w, info, ev,
+      // (mean-fold: from the last batch to the first — a row's seeds are the rows below it, k_wdist_mean_fold)
+      [&](uint64_t k) { return (fold ? n_batches - 1 - k : k) * B; },
+      [&](uint64_t base, uint64_t nb) {
+        const uint64_t s0 = (uint64_t)h_ptr[base], s1 = (uint64_t)h_ptr[base + nb];
+        if (s1 > s0)
+          hipLaunchKernelGGL(k_wdist_sources, dim3(grid_for(s1 - s0)), dim3(256), 0, c->stream, path_nodes, s0, s1, n,
+                             (const uint32_t*)step_path, (uint32_t)base, (uint32_t)B, dist, w.next);
+        return s1 > s0;
+      },
+      [&](uint64_t base, uint64_t nb) {  // the batch's rows of the tables
+        if (mean) {
+          hipLaunchKernelGGL(k_wdist_mean, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes, steps,
+                             n, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base,
+                             (double*)tables, D + K * K);
+          if (fold)
+            hipLaunchKernelGGL(k_wdist_mean_fold, dim3(grid_for(K * nb)), dim3(256), 0, c->stream, path_ptr, path_nodes,
+                               steps, n, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, (uint32_t)base,
+                               (double*)tables);
+        } else if (steps)
+          hipLaunchKernelGGL(k_wdist_min, dim3(grid_for(steps)), dim3(256), 0, c->stream, path_nodes, steps, n,
+                             (const uint32_t*)step_path, K, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb,
+                             (uint32_t)base, D);
+        return fold ? 2 : 1;  // (the min table's launch is counted even without steps)
+      });
 }
 
 static void wpath_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width,
@@ -530,17 +599,32 @@ static void wpath_distances(g2n_context* c, const void* indptr, const void* indi
   check_csr(who, index_width, n, nnz, !K || (path_ptr && tables && (!n || indptr)), !K || (indices && values), K != 0);
   if (K == 0) return;
   const uint64_t steps = path_steps_dev(c, who, path_ptr, K, path_nodes);
-  Events<3> ev;
-  ev.create();
-  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
-    wpath_distances_t(c, ip, ix, values, n, nnz, path_ptr, path_nodes, K, steps, mode, tables, info, ev.e);
+  weighted_search(c, index_width, indptr, indices, [&](auto* ip, auto* ix, hipEvent_t* ev) {
+    wpath_distances_t(c, ip, ix, values, n, nnz, path_ptr, path_nodes, K, steps, mode, tables, info, ev);
   });
-  G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
-// The two distance _host entries: the CSR (values: null for hops), the paths (S_DPP / S_DPN) and the
-// tables (S_DTAB, `cell` bytes a cell) on the shared context, search(c, csr, path_ptr, path_nodes,
-// tables) on them, and the tables copied back.
+// A distance _host entry's call on the shared context: fits() checks the output against the free
+// memory, the CSR is staged (values: null for hops), stage(c) puts the caller's two lists on the device
+// (S_DPP / S_DPN) and returns them, search(c, csr, first, second, out) runs on them with the output in
+// S_DTAB, and its `bytes` bytes are copied back.
+template <class Fits, class Stage, class Search>
+static int staged_call(int32_t device, const void* indptr, const void* indices, int32_t index_width,
+                       const double* values, uint64_t n, uint64_t nnz, uint64_t bytes, void* out, Fits&& fits,
+                       Stage&& stage, Search&& search) {
+  return host_call(device, [&](g2n_context* c) {
+    fits();
+    const StagedCsr d = stage_csr(c, indptr, indices, values, index_width, n, nnz);
+    const std::pair<const int64_t*, const int64_t*> lists = stage(c);
+    void* dout = dbuf(c, S_DTAB, (size_t)bytes);
+    search(c, d, lists.first, lists.second, dout);
+    if (bytes) G2N_HIP(hipMemcpyAsync(out, dout, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+// The two path _host entries: the paths in S_DPP / S_DPN, the tables `cell` bytes a cell;
+// search(c, csr, path_ptr, path_nodes, tables).
 template <class Search>
 static int distances_host(const std::string& who, const void* indptr, const void* indices, int32_t index_width,
                           const double* values, bool weighted, uint64_t n, uint64_t nnz, const int64_t* path_ptr,
@@ -551,19 +635,17 @@ static int distances_host(const std::string& who, const void* indptr, const void
   if (path_ptr[K] && !path_nodes) throw Failure(G2N_E_ARG, who + ": path_ptr out of range");
   const uint64_t steps = path_steps(who, path_ptr[0], path_ptr[K]);
   const uint64_t cell = mode != G2N_DIST_MIN ? 16 : weighted ? 8 : 4;
-  return host_call(device, [&](g2n_context* c) {
-    check_tables(who, K, cell);
-    const StagedCsr d = stage_csr(c, indptr, indices, values, index_width, n, nnz);
-    auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
-    auto* dpn = dget<int64_t>(c, S_DPN, steps);
-    const uint64_t tbytes = table_bytes(K, cell);
-    void* dtab = dbuf(c, S_DTAB, (size_t)tbytes);
-    G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
-    search(c, d, dpp, dpn, dtab);
-    if (tbytes) G2N_HIP(hipMemcpyAsync(out_tables, dtab, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-  });
+  return staged_call(
+      device, indptr, indices, index_width, values, n, nnz, table_bytes(K, cell), out_tables,
+      [&] { check_tables(who, K, cell); },
+      [&](g2n_context* c) {
+        auto* dpp = dget<int64_t>(c, S_DPP, K + 1);
+        auto* dpn = dget<int64_t>(c, S_DPN, steps);
+        G2N_HIP(hipMemcpyAsync(dpp, path_ptr, (size_t)(K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (steps) G2N_HIP(hipMemcpyAsync(dpn, path_nodes, (size_t)steps * 8, hipMemcpyHostToDevice, c->stream));
+        return std::make_pair((const int64_t*)dpp, (const int64_t*)dpn);
+      },
+      search);
 }
 
 int csr_path_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
@@ -602,35 +684,22 @@ static uint64_t pair_out_bytes(int32_t mode, bool weighted, uint64_t n_src, uint
   return n_src * n_tgt * (weighted ? 8 : 4);
 }
 
-// an output this library allocates must fit the device's free memory
 static void check_pair_out(const std::string& who, uint64_t bytes) {
-  size_t f = 0, t = 0;
-  G2N_HIP(hipMemGetInfo(&f, &t));
-  if (bytes > f)
-    throw Failure(G2N_E_UNSUPPORTED, who + ": the distance table exceeds the device's free memory");
+  check_fits(who, bytes, "the distance table exceeds");
 }
 
-// The caller's arrays, checked whole on the device before anything is searched or written (values:
-// null for hops); the targets' occurrences per node into tcnt (n + 1, cleared here; null: not wanted).
-template <class I>
-static void pair_check_on_device(g2n_context* c, const std::string& who, const I* indptr, const I* indices,
-                                 const double* values, uint64_t n, uint64_t nnz, const int64_t* sources, uint64_t n_src,
-                                 const int64_t* targets, uint64_t n_tgt, uint32_t* tcnt, DistState* st) {
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-  if (tcnt) G2N_HIP(hipMemsetAsync(tcnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(k_dist_check<I>, dim3(std::min(grid_for(std::max(n, nnz)), gcap)), dim3(256), 0, c->stream, indptr,
-                     indices, n, nnz, st);
-  if (values && nnz)
-    hipLaunchKernelGGL(k_wdist_values, dim3(std::min(grid_for(nnz), gcap)), dim3(256), 0, c->stream, values, nnz, st);
-  if (n_src)
-    hipLaunchKernelGGL(k_pair_ids, dim3(grid_for(n_src)), dim3(256), 0, c->stream, sources, n_src, n,
-                       (uint32_t*)nullptr, st);
-  if (n_tgt)
-    hipLaunchKernelGGL(k_pair_ids, dim3(grid_for(n_tgt)), dim3(256), 0, c->stream, targets, n_tgt, n, tcnt, st);
-  if (read_dev(c, st).bad)
-    throw Failure(G2N_E_ARG, who + ": indptr / indices / sources / targets out of range" +
-                                 (values ? ", or a value that is negative or not finite" : ""));
+// check_on_device's lists of a pair search: the targets' occurrences per node into tcnt (n + 1, cleared
+// here; null: not wanted)
+static auto pair_lists(g2n_context* c, const int64_t* sources, uint64_t n_src, const int64_t* targets, uint64_t n_tgt,
+                       uint64_t n, uint32_t* tcnt) {
+  return [=](DistState* st) {
+    if (tcnt) G2N_HIP(hipMemsetAsync(tcnt, 0, (n + 1) * sizeof(uint32_t), c->stream));
+    if (n_src)
+      hipLaunchKernelGGL(k_pair_ids, dim3(grid_for(n_src)), dim3(256), 0, c->stream, sources, n_src, n,
+                         (uint32_t*)nullptr, st);
+    if (n_tgt)
+      hipLaunchKernelGGL(k_pair_ids, dim3(grid_for(n_tgt)), dim3(256), 0, c->stream, targets, n_tgt, n, tcnt, st);
+  };
 }
 
 // g2n_csr_pair_distances on c's stream (the caller holds c's lock and opened the call); out: device.
@@ -640,10 +709,9 @@ static void pair_distances_t(g2n_context* c, const I* indptr, const I* indices, 
                              void* out, g2n_dist_info* info) {
   const std::string who = "g2n_csr_pair_distances";
   auto* st = dget<DistState>(c, S_DSTATE, 1);
-  const unsigned gcap = (unsigned)c->n_cu * 8;
   auto* tcnt = dget<uint32_t>(c, S_DCNT, n + 1);
-  pair_check_on_device(c, who, indptr, indices, (const double*)nullptr, n, nnz, sources, n_src, targets, n_tgt, tcnt,
-                       st);
+  check_on_device(c, who, indptr, indices, (const double*)nullptr, n, nnz, st, "sources / targets",
+                  pair_lists(c, sources, n_src, targets, n_tgt, n, tcnt));
   PairAcc acc{};
   acc.n_tgt = n_tgt;
   if (table) {  // the targets' positions sorted by node
@@ -665,54 +733,34 @@ static void pair_distances_t(g2n_context* c, const I* indptr, const I* indices, 
     acc.C = acc.S + n_src;
     if (n_src) G2N_HIP(hipMemsetAsync(out, 0, n_src * 16, c->stream));
   }
-  auto* seen = dget<unsigned long long>(c, S_DSEEN, n);
-  auto* next = dget<unsigned long long>(c, S_DNEXT, n);
-  auto* queue = dget<uint32_t>(c, S_DQUEUE, n);
-  auto* qmask = dget<unsigned long long>(c, S_DQMASK, n);
-  const uint64_t long_cap = nnz / kStatsShortRow + 1;
-  auto* long_rows = dget<uint32_t>(c, S_DLONG, long_cap);
-  const unsigned gn = std::min(grid_for(n), gcap);
-  int64_t launches = 0, levels = 0, batches = 0;
-  for (uint64_t base = 0; base < n_src; base += 64, batches++) {
-    acc.base = base;
-    acc.nb = (uint32_t)std::min<uint64_t>(64, n_src - base);
-    G2N_HIP(hipMemsetAsync(seen, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(next, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(st, 0, sizeof(DistState), c->stream));
-    if (n) {
-      hipLaunchKernelGGL(k_pair_sources, dim3(1), dim3(64), 0, c->stream, sources, base, base + acc.nb, n, seen, next);
-      launches++;
-    }
-    const uint32_t last = run_frontier(
-        c, who, st, n, n != 0, &launches,
-        [&](uint32_t L) {
-          if (table)
-            hipLaunchKernelGGL(k_pair_collect<true>, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc, st);
-          else
-            hipLaunchKernelGGL(k_pair_collect<false>, dim3(gn), dim3(256), 0, c->stream, next, n, L, queue, qmask, acc,
-                               st);
-        },
-        [&](uint32_t count) {
-          hipLaunchKernelGGL(k_dist_expand<I>, dim3(std::min(grid_for(count), gcap)), dim3(256), 0, c->stream, indptr,
-                             indices, n, nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
-                             long_rows, long_cap, st);
-          hipLaunchKernelGGL(k_dist_expand_long<I>, dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n,
-                             nnz, seen, next, (const uint32_t*)queue, (const unsigned long long*)qmask,
-                             (const uint32_t*)long_rows, long_cap, st);
-        },
-        [&](uint32_t budget) {
-          if (table)
-            hipLaunchKernelGGL((k_pair_narrow<I, true>), dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n,
-                               nnz, seen, next, queue, qmask, acc, st, budget);
-          else
-            hipLaunchKernelGGL((k_pair_narrow<I, false>), dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n,
-                               nnz, seen, next, queue, qmask, acc, st, budget);
-        });
-    levels = std::max<int64_t>(levels, last);
-  }
-  info->levels = levels;
-  info->launches = launches;
-  info->batches = batches;
+  const HopBufs b = hop_bufs(c, n, nnz);
+  const unsigned gn = std::min(grid_for(n), (unsigned)c->n_cu * 8);
+  hop_batches(
+      c, who, indptr, indices, n, nnz, b, (n_src + 63) / 64, info,
+      [&](uint64_t k) {  // (seeded whenever there are nodes: a batch of -1 ids alone is searched too)
+        acc.base = k * 64;
+        acc.nb = (uint32_t)std::min<uint64_t>(64, n_src - acc.base);
+        if (n)
+          hipLaunchKernelGGL(k_pair_sources, dim3(1), dim3(64), 0, c->stream, sources, acc.base, acc.base + acc.nb, n,
+                             b.seen, b.next);
+        return n != 0;
+      },
+      [&](uint32_t L) {
+        if (table)
+          hipLaunchKernelGGL(k_pair_collect<true>, dim3(gn), dim3(256), 0, c->stream, b.next, n, L, b.queue, b.qmask, acc,
+                             b.st);
+        else
+          hipLaunchKernelGGL(k_pair_collect<false>, dim3(gn), dim3(256), 0, c->stream, b.next, n, L, b.queue, b.qmask,
+                             acc, b.st);
+      },
+      [&](uint32_t budget) {
+        if (table)
+          hipLaunchKernelGGL((k_pair_narrow<I, true>), dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n,
+                             nnz, b.seen, b.next, b.queue, b.qmask, acc, b.st, budget);
+        else
+          hipLaunchKernelGGL((k_pair_narrow<I, false>), dim3(1), dim3(kDistNarrowTPB), 0, c->stream, indptr, indices, n,
+                             nnz, b.seen, b.next, b.queue, b.qmask, acc, b.st, budget);
+      });
 }
 
 static void pair_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width, uint64_t n,
@@ -724,17 +772,9 @@ static void pair_distances(g2n_context* c, const void* indptr, const void* indic
   const bool wants_out = pair_out_bytes(mode, false, n_src, n_tgt) != 0;
   check_csr(who, index_width, n, nnz, (!n_src || sources) && (!n_tgt || targets) && (!wants_out || out) && (!n || indptr),
             indices, true);
-  Events<2> ev;
-  ev.create();
-  G2N_HIP(hipEventRecord(ev.e[0], c->stream));
-  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
+  timed_hop_search(c, index_width, indptr, indices, info, [&](auto* ip, auto* ix) {
     pair_distances_t(c, ip, ix, n, nnz, sources, n_src, targets, n_tgt, mode == G2N_PAIR_TABLE, out, info);
   });
-  G2N_HIP(hipEventRecord(ev.e[1], c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  float ms = 0.f;
-  G2N_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  info->ms_bfs = ms;
 }
 
 // g2n_csr_pair_distances_weighted on c's stream; out: device, n_src x n_tgt float64, not written unless
@@ -744,49 +784,28 @@ static void wpair_distances_t(g2n_context* c, const I* indptr, const I* indices,
                               uint64_t nnz, const int64_t* sources, uint64_t n_src, const int64_t* targets,
                               uint64_t n_tgt, void* out, g2n_wdist_info* info, hipEvent_t* ev) {
   const std::string who = "g2n_csr_pair_distances_weighted";
-  const WSearchBufs w = wsearch_bufs(c, n, nnz);
+  const SearchBufs w = search_bufs(c, n, nnz);
   G2N_HIP(hipEventRecord(ev[0], c->stream));
-  const unsigned gcap = (unsigned)c->n_cu * 8;
-  pair_check_on_device(c, who, indptr, indices, values, n, nnz, sources, n_src, targets, n_tgt, (uint32_t*)nullptr,
-                       w.st);
+  check_on_device(c, who, indptr, indices, values, n, nnz, w.st, "sources / targets",
+                  pair_lists(c, sources, n_src, targets, n_tgt, n, (uint32_t*)nullptr));
   if (n_src == 0 || n_tgt == 0) return;
   const uint64_t B = wdist_batch_width(c, who, n, n_src);
   auto* dist = dget<unsigned long long>(c, S_WDIST, n * B);
   info->batch_paths = (int64_t)B;
-  int64_t launches = 0, rounds = 0, batches = 0;
-  double ms_search = 0.0, ms_tables = 0.0;
-  for (uint64_t base = 0; base < n_src; base += B, batches++) {
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, n_src - base);
-    if (batches) G2N_HIP(hipEventRecord(ev[0], c->stream));  // (the first batch's search time holds the checks)
-    hipLaunchKernelGGL(k_wdist_fill, dim3(std::min(grid_for(n * B), gcap)), dim3(256), 0, c->stream, dist, n * B,
-                       kWDistInf);
-    G2N_HIP(hipMemsetAsync(w.next, 0, n * 8, c->stream));
-    G2N_HIP(hipMemsetAsync(w.st, 0, sizeof(DistState), c->stream));
-    launches++;
-    if (n) {
-      hipLaunchKernelGGL(k_pair_wsources, dim3(1), dim3(64), 0, c->stream, sources, base, nb, n, (uint32_t)B, dist,
-                         w.next);
-      launches++;
-    }
-    const uint32_t last = wdist_search(c, who, indptr, indices, values, n, nnz, B, dist, w, n != 0, &launches);
-    rounds = std::max<int64_t>(rounds, last);
-    G2N_HIP(hipEventRecord(ev[1], c->stream));
-    hipLaunchKernelGGL(k_pair_wgather, dim3(std::min(grid_for(n_tgt * nb), gcap)), dim3(256), 0, c->stream, targets,
-                       n_tgt, n, (const unsigned long long*)dist, (uint32_t)B, nb, base, (unsigned long long*)out);
-    launches++;
-    G2N_HIP(hipEventRecord(ev[2], c->stream));
-    G2N_HIP(hipEventSynchronize(ev[2]));
-    float ms = 0.f;
-    G2N_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ms_search += ms;
-    G2N_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    ms_tables += ms;
-  }
-  info->rounds = rounds;
-  info->launches = launches;
-  info->batches = batches;
-  info->ms_search = ms_search;
-  info->ms_tables = ms_tables;
+  wdist_batches(
+      c, who, indptr, indices, values, n, nnz, n_src, B, dist, w, info, ev, [&](uint64_t k) { return k * B; },
+      [&](uint64_t base, uint64_t nb) {
+        if (n)
+          hipLaunchKernelGGL(k_pair_wsources, dim3(1), dim3(64), 0, c->stream, sources, base, (uint32_t)nb, n,
+                             (uint32_t)B, dist, w.next);
+        return n != 0;
+      },
+      [&](uint64_t base, uint64_t nb) {
+        hipLaunchKernelGGL(k_pair_wgather, dim3(std::min(grid_for(n_tgt * nb), (unsigned)c->n_cu * 8)), dim3(256), 0,
+                           c->stream, targets, n_tgt, n, (const unsigned long long*)dist, (uint32_t)B, (uint32_t)nb, base,
+                           (unsigned long long*)out);
+        return 1;
+      });
 }
 
 static void wpair_distances(g2n_context* c, const void* indptr, const void* indices, int32_t index_width,
@@ -799,17 +818,13 @@ static void wpair_distances(g2n_context* c, const void* indptr, const void* indi
   check_csr(who, index_width, n, nnz,
             (!n_src || sources) && (!n_tgt || targets) && (!n_src || !n_tgt || out) && (!n || indptr), indices && values,
             true);
-  Events<3> ev;
-  ev.create();
-  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) {
-    wpair_distances_t(c, ip, ix, values, n, nnz, sources, n_src, targets, n_tgt, out, info, ev.e);
+  weighted_search(c, index_width, indptr, indices, [&](auto* ip, auto* ix, hipEvent_t* ev) {
+    wpair_distances_t(c, ip, ix, values, n, nnz, sources, n_src, targets, n_tgt, out, info, ev);
   });
-  G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
-// The two pair _host entries: the CSR (values: null for hops), the two lists (S_DPN: the sources, then
-// the targets) and the output (S_DTAB) on the shared context, search(c, csr, sources, targets, out) on
-// them, and the output copied back.
+// The two pair _host entries: the two lists in S_DPN (the sources, then the targets);
+// search(c, csr, sources, targets, out).
 template <class Search>
 static int pairs_host(const std::string& who, const void* indptr, const void* indices, int32_t index_width,
                       const double* values, bool weighted, uint64_t n, uint64_t nnz, const int64_t* sources,
@@ -819,17 +834,15 @@ static int pairs_host(const std::string& who, const void* indptr, const void* in
   const uint64_t bytes = pair_out_bytes(mode, weighted, n_src, n_tgt);
   check_csr(who, index_width, n, nnz, indptr && (!n_src || sources) && (!n_tgt || targets) && (!bytes || out),
             indices && (!weighted || values), false);
-  return host_call(device, [&](g2n_context* c) {
-    check_pair_out(who, bytes);
-    const StagedCsr d = stage_csr(c, indptr, indices, values, index_width, n, nnz);
-    auto* ids = dget<int64_t>(c, S_DPN, n_src + n_tgt);
-    void* dout = dbuf(c, S_DTAB, (size_t)bytes);
-    if (n_src) G2N_HIP(hipMemcpyAsync(ids, sources, (size_t)n_src * 8, hipMemcpyHostToDevice, c->stream));
-    if (n_tgt) G2N_HIP(hipMemcpyAsync(ids + n_src, targets, (size_t)n_tgt * 8, hipMemcpyHostToDevice, c->stream));
-    search(c, d, ids, ids + n_src, dout);
-    if (bytes) G2N_HIP(hipMemcpyAsync(out, dout, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-  });
+  return staged_call(
+      device, indptr, indices, index_width, values, n, nnz, bytes, out, [&] { check_pair_out(who, bytes); },
+      [&](g2n_context* c) {
+        auto* ids = dget<int64_t>(c, S_DPN, n_src + n_tgt);
+        if (n_src) G2N_HIP(hipMemcpyAsync(ids, sources, (size_t)n_src * 8, hipMemcpyHostToDevice, c->stream));
+        if (n_tgt) G2N_HIP(hipMemcpyAsync(ids + n_src, targets, (size_t)n_tgt * 8, hipMemcpyHostToDevice, c->stream));
+        return std::make_pair((const int64_t*)ids, (const int64_t*)(ids + n_src));
+      },
+      search);
 }
 
 int csr_pair_distances_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
@@ -1064,6 +1077,20 @@ static void dist_result(g2n_context* c, const g2n_result& D, HostResult* H, cons
   G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
+// The end of a sequence search: cell [0][1] of the K = 2 table (device) and what the search reported
+template <class T>
+static void seq_search_end(g2n_context* c, const T* dtab, T* cell, g2n_seq_info* info, int64_t levels, int64_t launches,
+                           int64_t batches, double ms) {
+  T tab[4];
+  G2N_HIP(hipMemcpyAsync(tab, dtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
+  G2N_HIP(hipStreamSynchronize(c->stream));
+  *cell = tab[1];
+  info->levels = levels;
+  info->launches = launches;
+  info->batches = batches;
+  info->ms_bfs = ms;
+}
+
 // A sequence-distance build's result (g2n_seq_distance_from_path): the S records of the staged
 // input in[0, len) give the two lists of node ids (g2n_seq.hip), their names looked up in the key
 // table, and g2n_csr_path_distances searches the lists as K = 2.
@@ -1211,27 +1238,13 @@ static void seq_result(g2n_context* c, const g2n_result& D, HostResult* H, const
     g2n_wdist_info wi;
     wpath_distances(c, D.indptr, D.indices, D.index_width, (const double*)D.data, n, (uint64_t)D.nnz, dpp, dpn, 2,
                     G2N_DIST_MIN, wtab, &wi);
-    double tab[4];
-    G2N_HIP(hipMemcpyAsync(tab, wtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
-    G2N_HIP(hipStreamSynchronize(c->stream));
-    *q.wdist = tab[1];
-    q.info->levels = wi.rounds;
-    q.info->launches = wi.launches;
-    q.info->batches = wi.batches;
-    q.info->ms_bfs = wi.ms_search + wi.ms_tables;
+    seq_search_end(c, wtab, q.wdist, q.info, wi.rounds, wi.launches, wi.batches, wi.ms_search + wi.ms_tables);
     return;
   }
   auto* dtab = dget<uint32_t>(c, S_DTAB, 4);
   g2n_dist_info di;
   path_distances(c, D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dpp, dpn, 2, G2N_DIST_MIN, dtab, &di);
-  uint32_t tab[4];
-  G2N_HIP(hipMemcpyAsync(tab, dtab, sizeof(tab), hipMemcpyDeviceToHost, c->stream));
-  G2N_HIP(hipStreamSynchronize(c->stream));
-  *q.dist = tab[1];
-  q.info->levels = di.levels;
-  q.info->launches = di.launches;
-  q.info->batches = di.batches;
-  q.info->ms_bfs = di.ms_bfs;
+  seq_search_end(c, dtab, q.dist, q.info, di.levels, di.launches, di.batches, di.ms_bfs);
 }
 
 }  // namespace g2n
