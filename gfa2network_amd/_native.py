@@ -28,13 +28,14 @@ E_ARG, E_IO, E_GZIP, E_DEVICE, E_NOMEM, E_UNSUPPORTED = 13, 14, 15, 16, 17, 18
 
 DTYPE_CODES = {"bool": 0, "int8": 1, "int32": 2, "float32": 3, "float64": 4}
 CODE_DTYPES = {v: np.dtype(k) for k, v in DTYPE_CODES.items()}
-OUT_PARSE, OUT_CSR, OUT_COO, OUT_EDGE_LIST, OUT_GRAPH_JSON = 0, 1, 2, 3, 4
+OUT_PARSE, OUT_CSR, OUT_COO, OUT_EDGE_LIST, OUT_GRAPH_JSON, OUT_GRAPH_GEXF = 0, 1, 2, 3, 4, 5
 FMT_COO, FMT_CSR, FMT_TEXT = 0, 1, 2
 
 # every symbol include/g2n.h declares (tests check the library exports all of them)
 EXPORTED = [
     "g2n_version", "g2n_abi_version", "g2n_options_init", "g2n_device_count", "g2n_device_memory", "g2n_last_error",
     "g2n_status_name", "g2n_release_shared", "g2n_build_from_path", "g2n_build_from_buffer", "g2n_result_free",
+    "g2n_graph_gexf_from_path", "g2n_graph_gexf_from_buffer",
     "g2n_coo_to_csr", "g2n_coo_to_csr_band", "g2n_context_create", "g2n_context_destroy", "g2n_context_stream", "g2n_context_trim",
     "g2n_build_device", "g2n_build_decimal_range", "g2n_count_device", "g2n_order_keys", "g2n_rank_keys", "g2n_upload_file_range", "g2n_partition_keys", "g2n_dedup_keys", "g2n_gather_keys", "g2n_remap_pairs", "g2n_route_triplets", "g2n_csr_from_coo_pair",
     "g2n_context_group_slots", "g2n_route_group_slots", "g2n_csr_from_group_slots",
@@ -283,6 +284,12 @@ def load() -> ctypes.CDLL:
     lib.g2n_build_from_buffer.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Options),
                                           ctypes.POINTER(ctypes.POINTER(Result))]
     lib.g2n_build_from_buffer.restype = ctypes.c_int
+    lib.g2n_graph_gexf_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), ctypes.c_char_p, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_graph_gexf_from_path.restype = ctypes.c_int
+    lib.g2n_graph_gexf_from_buffer.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Options), ctypes.c_char_p,
+                                               ctypes.c_size_t, ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_graph_gexf_from_buffer.restype = ctypes.c_int
     lib.g2n_result_free.argtypes = [ctypes.POINTER(Result)]
     lib.g2n_result_free.restype = None
     lib.g2n_coo_to_csr.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
@@ -537,7 +544,7 @@ def _from_result(ptr, rc: int) -> RawResult:
     out.n_cast_overflow = int(r.n_cast_overflow)
     out.input_bytes = int(r.input_bytes)
     if r.format == FMT_TEXT and r.data:
-        out.format = "text"  # export: the edge-list lines (all, or those before a failure) or the JSON document
+        out.format = "text"  # export: the edge-list lines (all, or those before a failure) or the JSON / GEXF document
         out.data = _view(r.data, r.nnz, np.uint8, owner)
     elif r.status == OK:
         idx = np.int32 if r.index_width == 4 else np.int64
@@ -575,6 +582,24 @@ def build_from_buffer(data: bytes | bytearray | memoryview | np.ndarray, opts: O
     res = ctypes.POINTER(Result)()
     rc = lib.g2n_build_from_buffer(arr.ctypes.data if arr.size else None, arr.size, ctypes.byref(opts),
                                    ctypes.byref(res))
+    return _from_result(res, rc)
+
+
+def graph_gexf_from_path(path: str, opts: Options, head: bytes) -> RawResult:
+    """g2n_graph_gexf_from_path: the GEXF document (text) of the file's graph behind ``head``."""
+    lib = load()
+    res = ctypes.POINTER(Result)()
+    rc = lib.g2n_graph_gexf_from_path(os.fsencode(path), ctypes.byref(opts), head, len(head), ctypes.byref(res))
+    return _from_result(res, rc)
+
+
+def graph_gexf_from_buffer(data: bytes | bytearray | memoryview | np.ndarray, opts: Options, head: bytes) -> RawResult:
+    lib = load()
+    arr = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    arr = np.ascontiguousarray(arr, dtype=np.uint8)
+    res = ctypes.POINTER(Result)()
+    rc = lib.g2n_graph_gexf_from_buffer(arr.ctypes.data if arr.size else None, arr.size, ctypes.byref(opts), head,
+                                        len(head), ctypes.byref(res))
     return _from_result(res, rc)
 
 

@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "export_edge_list", "export_graph_json", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
+           "save_npz", "export_edge_list", "export_graph_json", "export_graph_gexf", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
            "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
@@ -1472,6 +1472,82 @@ def export_graph_json(gfa, output="-", *, bidirected: bool = False, keep_directe
         sys.stdout.buffer.flush()
     if raw_bytes_id and raw.n_nodes:
         raise TypeError("Object of type bytes is not JSON serializable")
+
+
+def _gexf_head(creator: str, lastmodified: str) -> bytes:
+    """What ``nx.write_gexf`` writes before the ``<graph>`` element (networkx/readwrite/gexf.py
+    GEXFWriter.__init__, version 1.2draft, prettyprint), with ElementTree's escapes: the date is an
+    attribute (``_escape_attrib``), the creator a text (``_escape_cdata``)."""
+    date = lastmodified.replace("&", "&amp;").replace("<", "&lt;").replace(">", "&gt;").replace('"', "&quot;")
+    date = date.replace("\r", "&#13;").replace("\n", "&#10;").replace("\t", "&#09;")
+    text = creator.replace("&", "&amp;").replace("<", "&lt;").replace(">", "&gt;")
+    head = ("<?xml version='1.0' encoding='utf-8'?>\n"
+            '<gexf xmlns="http://www.gexf.net/1.2draft" xmlns:xsi="http://www.w3.org/2001/XMLSchema-instance" '
+            'xsi:schemaLocation="http://www.gexf.net/1.2draft http://www.gexf.net/1.2draft/gexf.xsd" version="1.2">\n'
+            f'  <meta lastmodifieddate="{date}">\n'
+            f"    <creator>{text}</creator>\n"
+            "  </meta>\n")
+    return head.encode("utf-8", "xmlcharrefreplace")
+
+
+def export_graph_gexf(gfa, output, *, bidirected: bool = False, keep_directed_bidir: bool = False,
+                      raw_bytes_id: bool = False, device: int = 0, creator: str | None = None,
+                      lastmodified: str | None = None) -> None:
+    """``gfa2network [--raw-bytes-id] export GFA --format gexf [--bidirected [--keep-directed-bidir]]
+    --output PATH`` (cli.py:296-297): ``nx.write_gexf(G, PATH)`` of the graph ``parse_gfa(GFA,
+    build_graph=True, directed=True, ...)`` builds — the GEXF 1.2draft document Gephi reads, byte for
+    byte, without a graph object.  The graph, its node order and its edge order are ``export_graph_json``'s
+    (a ``DiGraph`` edge carries its last record's ``orientation_from`` / ``orientation_to``, a multigraph
+    edge its ``networkx_key``); the XML is rendered on the GPU from the same parse
+    (``G2N_OUT_GRAPH_GEXF``).  NetworkX's GEXF writer uses ``xml.etree.ElementTree`` only, so the bytes
+    depend on nothing but the graph and two strings, both arguments here (extensions):
+
+    * ``creator``: the ``<creator>`` text; ``None`` = ``f"NetworkX {networkx.__version__}"`` (when
+      networkx does not import, its ``ImportError`` is raised: the reference could not run either);
+    * ``lastmodified``: the ``lastmodifieddate``; ``None`` = ``time.strftime("%Y-%m-%d")``, taken when
+      the document is written.
+
+    Sources as ``export_graph_json``: a named file, ``"-"`` (stdin) or a file object.  ``output`` is a
+    path or a binary file object, as ``nx.write_gexf`` takes both.  The path ``"-"`` is a FILE named
+    ``-``: the reference passes ``args.output`` straight to ``nx.write_gexf``, so its default
+    ``--output -`` creates ``./-``; pass a file object such as ``sys.stdout.buffer`` to write to stdout.
+
+    As in the reference the graph is built first: the one-shot warning, then any error of the build (the
+    parser's, or the ASCII decode of a node key, whichever the stream meets first), which leaves no file;
+    the output is opened only after the build succeeded.  With ``raw_bytes_id`` the keys stay ``bytes`` and
+    the document holds ``str(key)``, the bytes repr (unlike JSON, a complete document).  A file whose
+    working set exceeds one GPU's free HBM raises ``NotImplementedError``.
+    """
+    if creator is None:
+        import networkx
+
+        creator = f"NetworkX {networkx.__version__}"
+    src = gfa
+    if not hasattr(gfa, "read") and str(gfa) == "-":
+        src = io.BytesIO(sys.stdin.buffer.read())  # parser.py:104: sys.stdin.buffer, not gunzipped
+    if not hasattr(src, "read"):
+        _stats_one_piece(src, device, "export_graph_gexf", "convert_format")
+    opts = nat.make_options(bidirected=bidirected, keep_directed_bidir=keep_directed_bidir,
+                            want_node_names=not raw_bytes_id, output=nat.OUT_GRAPH_GEXF, device=device)
+    # the head the device renders behind has the final length only when the date is given: the build gets a
+    # head of its own and the document's first bytes are composed again when it is written
+    built = _gexf_head(creator, lastmodified if lastmodified is not None else time.strftime("%Y-%m-%d"))
+    if hasattr(src, "read"):
+        raw = nat.graph_gexf_from_buffer(src.read(), opts, built)
+    else:
+        raw = nat.graph_gexf_from_path(str(src), opts, built)
+    _graph_pass(raw, raw_bytes_id, False, gfa)
+    if raw.format != "text" or raw.data is None or raw.data[:len(built)].tobytes() != built:
+        raise RuntimeError("export_graph_gexf: the build returned no document")
+    head = built if lastmodified is not None else _gexf_head(creator, time.strftime("%Y-%m-%d"))
+    body = memoryview(raw.data)[len(built):]
+    if hasattr(output, "write"):
+        output.write(head)
+        output.write(body)
+        return
+    with open(output, "wb") as fh:  # nx.write_gexf's open_file: any path, "-" included, names a file
+        fh.write(head)
+        fh.write(body)
 
 
 def _keep_index_dtype(M, raw):

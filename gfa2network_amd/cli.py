@@ -5,7 +5,8 @@ gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backen
 ``convert_format``, ``save_matrix`` (dense guard -> SystemExit), then the
 ``<matrix>.nodes.tsv`` sidecar.  ``export --format edge-list`` (cli.py:264-281) renders its
 lines on the GPU from the same parse, ``export --format json`` (cli.py:282-306) the graph's node-link
-document (``export_graph_json``); ``stats`` (cli.py:152-159, 364-376) prints
+document (``export_graph_json``), ``export --format gexf`` (cli.py:296-297) its GEXF document
+(``export_graph_gexf``); ``stats`` (cli.py:152-159, 364-376) prints
 ``compute_stats``'s six numbers, taken on the GPU from the CSR; ``distance --path``, ``distance
 --seq`` and ``distance-matrix`` (cli.py:161-189, 307-363) run their searches on the GPU over the same
 CSR (``--seq`` finds the nodes that carry the two sequences there too: ``sequence_distance``; an input
@@ -14,8 +15,11 @@ FileNotFoundError).  ``distance --path
 A B --method mean`` (extension; the default ``min`` prints what it printed) is ``genome_distance(...,
 method="mean")``.  As in
 the reference, ``distance`` and ``distance-matrix`` have no ``--weight-tag``: the functions take
-``weight_tag=``.  Graph outputs (``--graph``, export graphml / gexf) are outside the GPU
-GFA->CSR path.
+``weight_tag=``.  Of the two XML exports gexf is served: NetworkX writes it with
+``xml.etree.ElementTree`` alone, so its bytes depend on the graph, the NetworkX version (the creator
+string) and the date only, and ``export_graph_gexf`` takes both as arguments.  graphml stays out:
+``nx.write_graphml`` picks lxml or ElementTree, whichever it finds, and its bytes differ.  ``--graph``
+(a NetworkX object) is outside the GPU GFA->CSR path.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ import sys
 from pathlib import Path
 
 from . import __version__
-from .api import (compute_stats, convert_format, export_edge_list, export_graph_json, genome_distance, genome_distance_matrix, parse_gfa,
+from .api import (compute_stats, convert_format, export_edge_list, export_graph_gexf, export_graph_json, genome_distance, genome_distance_matrix, parse_gfa,
                   parse_gfa_names, save_matrix, save_node_map_native, sequence_distance)
 
 
@@ -107,8 +111,14 @@ def main(argv: list[str] | None = None) -> None:
                               keep_directed_bidir=args.keep_directed_bidir, raw_bytes_id=args.raw_bytes_id,
                               device=args.device)
             return
+        if args.format == "gexf":  # cli.py:296-297: args.output goes to nx.write_gexf as it is ("-" names a file)
+            export_graph_gexf(args.gfa, args.output, bidirected=args.bidirected,
+                              keep_directed_bidir=args.keep_directed_bidir, raw_bytes_id=args.raw_bytes_id,
+                              device=args.device)
+            return
         if args.format != "edge-list":
-            parser.error(f"export --format {args.format} builds a NetworkX graph, outside the GPU GFA->CSR path")
+            parser.error(f"export --format {args.format}: nx.write_graphml's bytes depend on the XML library NetworkX "
+                         "finds (lxml or ElementTree); it stays with the reference")
         export_edge_list(args.gfa, args.output, bidirected=args.bidirected, device=args.device)
         return
     if args.cmd == "stats":  # cli.py:364-376 (the alias reaches no branch there either)

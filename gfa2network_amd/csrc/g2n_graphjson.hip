@@ -574,6 +574,91 @@ static int gj_build(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_o
   return R->status;
 }
 
+// O1, O2: the orientation spans of the m L/E/C records, in stream order
+static const GjOri* gj_spans(g2n_context* c, const uint8_t* in, uint64_t len, uint64_t m) {
+  const uint64_t nb = grid_for((len + kGjChunk - 1) / kGjChunk);
+  auto* bcnt = dget<uint32_t>(c, S_GJBCNT, nb + 1);
+  auto* boff = dget<uint32_t>(c, S_GJBOFF, nb + 1);
+  hipLaunchKernelGGL(k_gj_line_count, dim3((unsigned)nb), dim3(kTPB), 0, c->stream, in, len, bcnt);
+  G2N_HIP(hipMemsetAsync(bcnt + nb, 0, sizeof(uint32_t), c->stream));
+  scan_excl<uint32_t, uint32_t>(c, bcnt, boff, nb + 1);
+  if ((uint64_t)read_dev(c, boff + nb) != m) throw Failure(G2N_E_DEVICE, "graph JSON: L/E/C lines differ from the build's entries");
+  auto* starts = dget<uint64_t>(c, S_GJSTART, m);
+  auto* spans = dget<GjOri>(c, S_GJORI, m);
+  auto* badf = dget<unsigned int>(c, S_ZBAD, 1);
+  G2N_HIP(hipMemsetAsync(badf, 0, sizeof(unsigned int), c->stream));
+  hipLaunchKernelGGL(k_gj_line_starts, dim3((unsigned)nb), dim3(kTPB), 0, c->stream, in, len, (const uint32_t*)boff, m,
+                     starts);
+  hipLaunchKernelGGL(k_gj_ori, dim3(grid_for(m, 64)), dim3(64), 0, c->stream, in, len, (const uint64_t*)starts, m, spans,
+                     badf);
+  if (read_dev(c, badf)) throw Failure(G2N_E_DEVICE, "graph JSON: a record of a clean build did not parse again");
+  return spans;
+}
+
+// G1-G7: the links in listing order (ls, lt: source and target ids; lx: the key (multi) or the record of the
+// group's last entry).  Entry i is COO triplet i * step; unordered: the pair's source is its smaller id.
+struct GjLinks {
+  uint64_t n_links = 0;
+  uint32_t *ls = nullptr, *lt = nullptr, *lx = nullptr;
+};
+
+static GjLinks gj_links(g2n_context* c, const int32_t* rows, const int32_t* cols, uint64_t m, uint32_t step,
+                        bool unordered, bool multi, uint64_t n) {
+  GjLinks K;
+  if (!m) return K;
+  const int bits = bits_for(n);
+  auto* cr = dget<uint32_t>(c, S_GJCR, m);
+  auto* cc = dget<uint32_t>(c, S_GJCC, m);
+  auto* idx = dget<uint32_t>(c, S_GJIDX, m);
+  auto* k1 = dget<uint32_t>(c, S_GJK1, m);    // c sorted; later the sources in stream order of the first entries
+  auto* idx1 = dget<uint32_t>(c, S_GJIDX1, m);
+  auto* k2 = dget<uint32_t>(c, S_GJK2, m);    // r in c order; later the groups beside k1
+  auto* rs = dget<uint32_t>(c, S_GJRS, m);
+  auto* perm = dget<uint32_t>(c, S_GJPERM, m);
+  auto* head = dget<uint32_t>(c, S_GJHEAD, m + 1);
+  auto* hx = dget<uint32_t>(c, S_GJHX, m + 1);
+  auto* hs = dget<uint32_t>(c, S_GJHS, m + 1);
+  auto* fflag = dget<uint32_t>(c, S_GJFFLAG, m + 1);
+  auto* fx = dget<uint32_t>(c, S_GJFX, m + 1);
+  auto* fgroup = dget<uint32_t>(c, S_GJFGRP, m);
+  hipLaunchKernelGGL(k_gj_keys, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, rows, cols, m, step, (int)unordered,
+                     cr, cc, idx);
+  sort_pairs_u32<uint32_t>(c, cc, k1, idx, idx1, m, bits);
+  hipLaunchKernelGGL(k_gj_gather, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, (const uint32_t*)cr,
+                     (const uint32_t*)idx1, m, k2);
+  sort_pairs_u32<uint32_t>(c, k2, rs, idx1, perm, m, bits);
+  hipLaunchKernelGGL(k_gj_heads, dim3(grid_for(m + 1)), dim3(kTPB), 0, c->stream, (const uint32_t*)rs,
+                     (const uint32_t*)cc, (const uint32_t*)perm, m, head);
+  scan_excl<uint32_t, uint32_t>(c, head, hx, m + 1);
+  const uint64_t G = read_dev(c, hx + m);
+  G2N_HIP(hipMemsetAsync(fflag, 0, (m + 1) * sizeof(uint32_t), c->stream));
+  hipLaunchKernelGGL(k_gj_first_mark, dim3(grid_for(m + 1)), dim3(kTPB), 0, c->stream, (const uint32_t*)head,
+                     (const uint32_t*)hx, (const uint32_t*)perm, m, hs, fflag, fgroup);
+  scan_excl<uint32_t, uint32_t>(c, fflag, fx, m + 1);
+  uint32_t *lr = k1, *lg = k2;  // (both sorts are done with them)
+  hipLaunchKernelGGL(k_gj_first_compact, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, (const uint32_t*)fflag,
+                     (const uint32_t*)fx, (const uint32_t*)fgroup, (const uint32_t*)cr, m, lr, lg);
+  auto* lrs = dget<uint32_t>(c, S_GJLRS, G);
+  auto* order = dget<uint32_t>(c, S_GJORDER, G);
+  sort_pairs_u32<uint32_t>(c, lr, lrs, lg, order, G, bits);
+  auto* cnt = dget<uint32_t>(c, S_GJCNT, G + 1);
+  auto* base = dget<uint32_t>(c, S_GJBASE, G + 1);
+  auto* gbase = dget<uint32_t>(c, S_GJGBASE, G);
+  hipLaunchKernelGGL(k_gj_counts, dim3(grid_for(G + 1)), dim3(kTPB), 0, c->stream, (const uint32_t*)order,
+                     (const uint32_t*)hs, G, (int)multi, cnt);
+  scan_excl<uint32_t, uint32_t>(c, cnt, base, G + 1);
+  hipLaunchKernelGGL(k_gj_gbase, dim3(grid_for(G)), dim3(kTPB), 0, c->stream, (const uint32_t*)order,
+                     (const uint32_t*)base, G, gbase);
+  K.n_links = multi ? m : G;
+  K.ls = dget<uint32_t>(c, S_GJLS, K.n_links);
+  K.lt = dget<uint32_t>(c, S_GJLT, K.n_links);
+  K.lx = dget<uint32_t>(c, S_GJLX, K.n_links);
+  hipLaunchKernelGGL(k_gj_emit, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, (const uint32_t*)rs, (const uint32_t*)cc,
+                     (const uint32_t*)perm, (const uint32_t*)head, (const uint32_t*)hx, (const uint32_t*)hs,
+                     (const uint32_t*)gbase, m, K.n_links, (int)multi, K.ls, K.lt, K.lx);
+  return K;
+}
+
 // G2N_OUT_GRAPH_JSON.  Result: format G2N_FMT_TEXT, data = the document, nnz = its bytes.
 static int run_graph_json(g2n_context* c, const uint8_t* in, uint64_t len, const g2n_options* o, g2n_result* R) {
   const bool keys_str = o->want_node_names != 0;
@@ -614,83 +699,13 @@ static int run_graph_json(g2n_context* c, const uint8_t* in, uint64_t len, const
   if (n && (!blob || !offs)) throw Failure(G2N_E_DEVICE, "graph JSON: the build returned no names");
 
   // ---- O1, O2: the records' orientation spans (plain mode: entry k is record k)
-  const GjOri* ori = nullptr;
-  if (!multi && m) {
-    const uint64_t nb = grid_for((len + kGjChunk - 1) / kGjChunk);
-    auto* bcnt = dget<uint32_t>(c, S_GJBCNT, nb + 1);
-    auto* boff = dget<uint32_t>(c, S_GJBOFF, nb + 1);
-    hipLaunchKernelGGL(k_gj_line_count, dim3((unsigned)nb), dim3(kTPB), 0, c->stream, in, len, bcnt);
-    G2N_HIP(hipMemsetAsync(bcnt + nb, 0, sizeof(uint32_t), c->stream));
-    scan_excl<uint32_t, uint32_t>(c, bcnt, boff, nb + 1);
-    if ((uint64_t)read_dev(c, boff + nb) != m) throw Failure(G2N_E_DEVICE, "graph JSON: L/E/C lines differ from the build's entries");
-    auto* starts = dget<uint64_t>(c, S_GJSTART, m);
-    auto* spans = dget<GjOri>(c, S_GJORI, m);
-    auto* badf = dget<unsigned int>(c, S_ZBAD, 1);
-    G2N_HIP(hipMemsetAsync(badf, 0, sizeof(unsigned int), c->stream));
-    hipLaunchKernelGGL(k_gj_line_starts, dim3((unsigned)nb), dim3(kTPB), 0, c->stream, in, len, (const uint32_t*)boff, m,
-                       starts);
-    hipLaunchKernelGGL(k_gj_ori, dim3(grid_for(m, 64)), dim3(64), 0, c->stream, in, len, (const uint64_t*)starts, m, spans,
-                       badf);
-    if (read_dev(c, badf)) throw Failure(G2N_E_DEVICE, "graph JSON: a record of a clean build did not parse again");
-    ori = spans;
-  }
+  const GjOri* ori = !multi && m ? gj_spans(c, in, len, m) : nullptr;
   phase(c, "gj_spans");
 
   // ---- G1-G7: the links in listing order
-  uint64_t n_links = 0;
-  uint32_t *ls = nullptr, *lt = nullptr, *lx = nullptr;
-  if (m) {
-    const int bits = bits_for(n);
-    auto* cr = dget<uint32_t>(c, S_GJCR, m);
-    auto* cc = dget<uint32_t>(c, S_GJCC, m);
-    auto* idx = dget<uint32_t>(c, S_GJIDX, m);
-    auto* k1 = dget<uint32_t>(c, S_GJK1, m);    // c sorted; later the sources in stream order of the first entries
-    auto* idx1 = dget<uint32_t>(c, S_GJIDX1, m);
-    auto* k2 = dget<uint32_t>(c, S_GJK2, m);    // r in c order; later the groups beside k1
-    auto* rs = dget<uint32_t>(c, S_GJRS, m);
-    auto* perm = dget<uint32_t>(c, S_GJPERM, m);
-    auto* head = dget<uint32_t>(c, S_GJHEAD, m + 1);
-    auto* hx = dget<uint32_t>(c, S_GJHX, m + 1);
-    auto* hs = dget<uint32_t>(c, S_GJHS, m + 1);
-    auto* fflag = dget<uint32_t>(c, S_GJFFLAG, m + 1);
-    auto* fx = dget<uint32_t>(c, S_GJFX, m + 1);
-    auto* fgroup = dget<uint32_t>(c, S_GJFGRP, m);
-    hipLaunchKernelGGL(k_gj_keys, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, rows, cols, m, step, (int)(multi && !directed),
-                       cr, cc, idx);
-    sort_pairs_u32<uint32_t>(c, cc, k1, idx, idx1, m, bits);
-    hipLaunchKernelGGL(k_gj_gather, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, (const uint32_t*)cr,
-                       (const uint32_t*)idx1, m, k2);
-    sort_pairs_u32<uint32_t>(c, k2, rs, idx1, perm, m, bits);
-    hipLaunchKernelGGL(k_gj_heads, dim3(grid_for(m + 1)), dim3(kTPB), 0, c->stream, (const uint32_t*)rs,
-                       (const uint32_t*)cc, (const uint32_t*)perm, m, head);
-    scan_excl<uint32_t, uint32_t>(c, head, hx, m + 1);
-    const uint64_t G = read_dev(c, hx + m);
-    G2N_HIP(hipMemsetAsync(fflag, 0, (m + 1) * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_gj_first_mark, dim3(grid_for(m + 1)), dim3(kTPB), 0, c->stream, (const uint32_t*)head,
-                       (const uint32_t*)hx, (const uint32_t*)perm, m, hs, fflag, fgroup);
-    scan_excl<uint32_t, uint32_t>(c, fflag, fx, m + 1);
-    uint32_t *lr = k1, *lg = k2;  // (both sorts are done with them)
-    hipLaunchKernelGGL(k_gj_first_compact, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, (const uint32_t*)fflag,
-                       (const uint32_t*)fx, (const uint32_t*)fgroup, (const uint32_t*)cr, m, lr, lg);
-    auto* lrs = dget<uint32_t>(c, S_GJLRS, G);
-    auto* order = dget<uint32_t>(c, S_GJORDER, G);
-    sort_pairs_u32<uint32_t>(c, lr, lrs, lg, order, G, bits);
-    auto* cnt = dget<uint32_t>(c, S_GJCNT, G + 1);
-    auto* base = dget<uint32_t>(c, S_GJBASE, G + 1);
-    auto* gbase = dget<uint32_t>(c, S_GJGBASE, G);
-    hipLaunchKernelGGL(k_gj_counts, dim3(grid_for(G + 1)), dim3(kTPB), 0, c->stream, (const uint32_t*)order,
-                       (const uint32_t*)hs, G, (int)multi, cnt);
-    scan_excl<uint32_t, uint32_t>(c, cnt, base, G + 1);
-    hipLaunchKernelGGL(k_gj_gbase, dim3(grid_for(G)), dim3(kTPB), 0, c->stream, (const uint32_t*)order,
-                       (const uint32_t*)base, G, gbase);
-    n_links = multi ? m : G;
-    ls = dget<uint32_t>(c, S_GJLS, n_links);
-    lt = dget<uint32_t>(c, S_GJLT, n_links);
-    lx = dget<uint32_t>(c, S_GJLX, n_links);
-    hipLaunchKernelGGL(k_gj_emit, dim3(grid_for(m)), dim3(kTPB), 0, c->stream, (const uint32_t*)rs, (const uint32_t*)cc,
-                       (const uint32_t*)perm, (const uint32_t*)head, (const uint32_t*)hx, (const uint32_t*)hs,
-                       (const uint32_t*)gbase, m, n_links, (int)multi, ls, lt, lx);
-  }
+  const GjLinks K = gj_links(c, rows, cols, m, step, multi && !directed, multi, n);
+  const uint64_t n_links = K.n_links;
+  const uint32_t *ls = K.ls, *lt = K.lt, *lx = K.lx;
   phase(c, "gj_order");
 
   // ---- T1-T3: the text

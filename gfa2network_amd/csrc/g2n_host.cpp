@@ -180,7 +180,7 @@ static int check_opts(const g2n_options* o) {
     g2n::set_last_error("g2n_options: unsupported dtype");
     return G2N_E_ARG;
   }
-  if (o->output < G2N_OUT_PARSE || o->output > G2N_OUT_GRAPH_JSON) {
+  if (o->output < G2N_OUT_PARSE || o->output > G2N_OUT_GRAPH_GEXF) {
     g2n::set_last_error("g2n_options: unknown output");
     return G2N_E_ARG;
   }
@@ -294,6 +294,39 @@ int g2n_build_from_path(const char* path, const g2n_options* opts, g2n_result** 
   int rc = check_opts(opts);
   if (rc) return rc;
   return build_from_path(path, opts, out);
+}
+
+// export --format gexf: the build with output G2N_OUT_GRAPH_GEXF, the document's head set for its duration
+namespace {
+struct GexfScope {
+  g2n::GexfHead head;
+  g2n_options o;
+  GexfScope(const g2n_options* opts, const void* p, size_t n) : head{(const uint8_t*)p, (uint64_t)n}, o(*opts) {
+    o.output = G2N_OUT_GRAPH_GEXF;
+    g2n::set_gexf_head(&head);
+  }
+  ~GexfScope() { g2n::set_gexf_head(nullptr); }
+};
+}  // namespace
+
+int g2n_graph_gexf_from_path(const char* path, const g2n_options* opts, const void* head, size_t head_len,
+                             g2n_result** out) {
+  if (!out || !path || (head_len && !head)) return G2N_E_ARG;
+  *out = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  GexfScope scope(opts, head, head_len);
+  return build_from_path(path, &scope.o, out);
+}
+
+int g2n_graph_gexf_from_buffer(const void* buf, size_t len, const g2n_options* opts, const void* head, size_t head_len,
+                               g2n_result** out) {
+  if (!out || (len && !buf) || (head_len && !head)) return G2N_E_ARG;
+  *out = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  GexfScope scope(opts, head, head_len);
+  return g2n::guarded([&] { return g2n::build_host(buf, len, &scope.o, out, 0.0); });
 }
 
 int g2n_stats_from_path(const char* path, const g2n_options* opts, g2n_graph_stats* stats, int64_t* n_paths,

@@ -109,6 +109,14 @@ struct StatsRequest {
 };
 void set_stats_request(const StatsRequest* req);  // nullptr: none (thread-local)
 
+// g2n_graph_gexf_from_path / _from_buffer: while set on the calling thread, a G2N_OUT_GRAPH_GEXF build opens
+// its document with these bytes (host; the XML declaration through </meta>, a newline behind it).
+struct GexfHead {
+  const uint8_t* p;
+  uint64_t n;
+};
+void set_gexf_head(const GexfHead* head);  // nullptr: none (thread-local)
+
 // g2n_distances_from_path: the same, for path distances.  The build's CSR and names stay on the
 // device; the K paths' step names (host blob + offsets, sources first) are looked up in the names
 // there, and g2n_csr_path_distances runs on the ids.  Only the tables and the scalars come back.

@@ -55,7 +55,7 @@ enum Slot {
   S_DFLAG, S_DKS, S_DSBLOB, S_DSOFFS, S_DIDS,  // g2n_distances_from_path: the step lookup
   S_GJKEY, S_GJBCNT, S_GJBOFF, S_GJSTART, S_GJORI, S_GJCR, S_GJCC, S_GJIDX, S_GJK1, S_GJIDX1, S_GJK2, S_GJRS, S_GJPERM,
   S_GJHEAD, S_GJHX, S_GJHS, S_GJFFLAG, S_GJFX, S_GJFGRP, S_GJLRS, S_GJORDER, S_GJCNT, S_GJBASE, S_GJGBASE, S_GJLS, S_GJLT,
-  S_GJLX, S_GJHEADSTR,  // G2N_OUT_GRAPH_JSON (g2n_graphjson.hip)
+  S_GJLX, S_GJHEADSTR,  // G2N_OUT_GRAPH_JSON (g2n_graphjson.hip), G2N_OUT_GRAPH_GEXF (g2n_graphgexf.hip)
   S_QSTATE, S_QLINES, S_QNODE, S_QFPOS, S_QFLAG, S_QLAST, S_QCAND, S_QIDS, S_QBYTES, S_QNLEN, S_QNOFF, S_QNBLOB,  // g2n_seq_distance_from_path (g2n_seq.hip)
   S_NSLOTS
 };
@@ -2274,6 +2274,8 @@ static int run_edge_list(g2n_context* c, const uint8_t* in, uint64_t len, const 
 
 // export --format json: the graph's node-link document, ordered and rendered in HBM (G2N_OUT_GRAPH_JSON)
 #include "g2n_graphjson.hip"
+// export --format gexf: the same graph as the document nx.write_gexf writes (G2N_OUT_GRAPH_GEXF)
+#include "g2n_graphgexf.hip"
 
 namespace g2n {
 
@@ -2281,6 +2283,7 @@ static int run_pipeline(g2n_context* c, const uint8_t* in, uint64_t len, const g
   c->slots = GroupedCoo{};  // (set again only by a build whose COO result stays in group slots)
   if (o->output == G2N_OUT_EDGE_LIST) return run_edge_list(c, in, len, o, R);
   if (o->output == G2N_OUT_GRAPH_JSON) return run_graph_json(c, in, len, o, R);
+  if (o->output == G2N_OUT_GRAPH_GEXF) return run_graph_gexf(c, in, len, o, R);
   return run_build(c, in, len, o, R);
 }
 

@@ -45,6 +45,15 @@
  *                  that has a node carries no text (data = NULL, n_nodes > 0): json.dump writes
  *                  up to the first node's id and raises TypeError.  Limits: fewer than 2^32 - 1
  *                  entries (add_edge calls) and 2^31 - 1 nodes, else G2N_E_UNSUPPORTED.
+ *   G2N_OUT_GRAPH_GEXF  the bytes `gfa2network export --format gexf [--bidirected
+ *                  [--keep-directed-bidir]]` writes (cli.py:296-297): nx.write_gexf(G, path) with
+ *                  its defaults (utf-8, prettyprint, version 1.2draft) for the same graph, its
+ *                  nodes and edges in the same order as the JSON document's.  The document opens
+ *                  with a head that holds the date and the NetworkX version, so this output is
+ *                  built through g2n_graph_gexf_from_path / _from_buffer, which take the head
+ *                  (G2N_E_ARG from the plain build entry points).  Options, result, errors and
+ *                  limits as G2N_OUT_GRAPH_JSON's, except that bytes keys (want_node_names = 0)
+ *                  give a complete document: a key is written as str(key), the bytes repr.
  *
  * Errors: a non-zero status is one of G2N_E_*; each maps 1:1 to the exception the
  * reference raises for the same input (type + message; the Python shim re-raises it).
@@ -91,7 +100,14 @@ enum {
 /* ---- matrix dtypes (cli.py:92-97 --dtype choices) ------------------------------------ */
 enum { G2N_BOOL = 0, G2N_INT8 = 1, G2N_INT32 = 2, G2N_FLOAT32 = 3, G2N_FLOAT64 = 4 };
 
-enum { G2N_OUT_PARSE = 0, G2N_OUT_CSR = 1, G2N_OUT_COO = 2, G2N_OUT_EDGE_LIST = 3, G2N_OUT_GRAPH_JSON = 4 };
+enum {
+  G2N_OUT_PARSE = 0,
+  G2N_OUT_CSR = 1,
+  G2N_OUT_COO = 2,
+  G2N_OUT_EDGE_LIST = 3,
+  G2N_OUT_GRAPH_JSON = 4,
+  G2N_OUT_GRAPH_GEXF = 5
+};
 enum { G2N_FMT_COO = 0, G2N_FMT_CSR = 1, G2N_FMT_TEXT = 2 };
 
 /* Mirrors parse_gfa's keyword arguments that affect the matrix (builders.py:30-50). */
@@ -233,6 +249,15 @@ const char *g2n_status_name(int status);
  * read raw — the same rule as parser.py:100-112 (by name, not by magic bytes). */
 int g2n_build_from_path(const char *path, const g2n_options *opts, g2n_result **out);
 int g2n_build_from_buffer(const void *buf, size_t len, const g2n_options *opts, g2n_result **out);
+/* export --format gexf: the same two with opts->output taken as G2N_OUT_GRAPH_GEXF.  head (head_len bytes,
+ * host) opens the document: everything nx.write_gexf writes before the <graph> element — the XML
+ * declaration, the <gexf ...> tag and the <meta lastmodifieddate="DATE"><creator>...</creator></meta>
+ * block, each line with its newline — already escaped; it is copied as it is.  The result's text
+ * (G2N_FMT_TEXT) is the whole document, the head included. */
+int g2n_graph_gexf_from_path(const char *path, const g2n_options *opts, const void *head, size_t head_len,
+                             g2n_result **out);
+int g2n_graph_gexf_from_buffer(const void *buf, size_t len, const g2n_options *opts, const void *head,
+                               size_t head_len, g2n_result **out);
 void g2n_result_free(g2n_result *res);
 
 /* gzip.open(...).read() of an in-memory .gz file (parser.py:108-109): the reader that
