@@ -48,6 +48,7 @@ EXPORTED = [
     "g2n_graph_weights_from_path", "g2n_wdistances_from_path", "g2n_seq_wdistance_from_path",
     "g2n_csr_pair_distances", "g2n_csr_pair_distances_weighted", "g2n_csr_pair_distances_host",
     "g2n_csr_pair_distances_weighted_host", "g2n_pair_distances_from_path",
+    "g2n_write_dense", "g2n_dense_range", "g2n_dense_last_times", "g2n_format_g6",
 ]
 
 
@@ -198,6 +199,19 @@ class SeqInfo(ctypes.Structure):
     ]
 
 
+class DenseInfo(ctypes.Structure):
+    """g2n_dense_info (include/g2n.h)."""
+
+    _fields_ = [
+        ("doc_bytes", ctypes.c_uint64),
+        ("bands", ctypes.c_uint64),
+        ("tile_bytes", ctypes.c_uint64),
+        ("band_bytes", ctypes.c_uint64),
+        ("declined", ctypes.c_int32),
+    ]
+
+
+DENSE_CSV, DENSE_NPY = 0, 1
 DIST_MIN, DIST_MEAN, DIST_MEAN_FOLD = 0, 1, 2  # (MEAN_FOLD: the weighted searches only)
 
 _lib = None
@@ -320,6 +334,15 @@ def load() -> ctypes.CDLL:
     lib.g2n_route_triplets.argtypes = [P, P, P, P, U64, I32, P, U64, U32, I32, P, P, P, P]
     lib.g2n_csr_from_coo_pair.argtypes = [P, P, P, P, U64, P, P, P, U64, I32, I64, U64, U64, I32, I32, I32,
                                           ctypes.POINTER(Result)]
+    lib.g2n_write_dense.argtypes = [ctypes.c_char_p, I32, P, ctypes.c_size_t, P, P, I32, P, I32, U64, U64, U64, I32,
+                                    ctypes.POINTER(DenseInfo)]
+    lib.g2n_write_dense.restype = ctypes.c_int
+    lib.g2n_dense_range.argtypes = [I32, P, P, I32, P, I32, U64, U64, I32, U64, U64, P, ctypes.POINTER(DenseInfo)]
+    lib.g2n_dense_range.restype = ctypes.c_int
+    lib.g2n_dense_last_times.argtypes = [ctypes.POINTER(ctypes.c_double * 5)]
+    lib.g2n_dense_last_times.restype = None
+    lib.g2n_format_g6.argtypes = [ctypes.c_double, P]
+    lib.g2n_format_g6.restype = ctypes.c_uint32
     lib.g2n_release_shared.argtypes = [I32, ctypes.POINTER(U64)]
     lib.g2n_release_shared.restype = ctypes.c_int
     lib.g2n_context_group_slots.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
@@ -1228,6 +1251,71 @@ def first_bad_utf8(blob: np.ndarray, offsets: np.ndarray) -> int:
     if n <= 0:
         return -1
     return int(load().g2n_first_bad_utf8(blob.ctypes.data if blob.size else None, offsets.ctypes.data, n))
+
+
+def format_g6(v: float) -> bytes:
+    """Python's ``'%.6g' % v`` from the code the device runs (g2n_format_g6, csrc/g6fmt.h)."""
+    out = (ctypes.c_uint8 * 16)()
+    n = load().g2n_format_g6(float(v), out)
+    return bytes(out[:n])
+
+
+def _dense_args(indptr: np.ndarray, indices: np.ndarray, data: np.ndarray, n_rows: int):
+    """A host CSR with values as the dense writers take it: contiguous arrays, the index width and the dtype code."""
+    dt = np.dtype(data.dtype)
+    if dt.name not in DTYPE_CODES:
+        raise NotImplementedError(f"GPU dense writers support {sorted(DTYPE_CODES)}, not {dt}")
+    ip, ix, _none, idt = _csr_args(indptr, indices, n_rows)
+    val = np.ascontiguousarray(data)
+    if len(val) != len(ix) or int(ip[n_rows]) != len(ix):
+        raise ValueError("indptr[n_rows] must count the indices and the values")
+    return ip, ix, val, idt.itemsize, DTYPE_CODES[dt.name]
+
+
+def _dense_info(info: DenseInfo) -> dict:
+    return {"doc_bytes": int(info.doc_bytes), "bands": int(info.bands), "tile_bytes": int(info.tile_bytes),
+            "band_bytes": int(info.band_bytes), "declined": int(info.declined)}
+
+
+def write_dense(path: str, kind: int, head: bytes, indptr: np.ndarray, indices: np.ndarray, data: np.ndarray,
+                n_rows: int, n_cols: int, band_bytes: int = 0, device: int = 0) -> dict:
+    """g2n_write_dense: the dense csv (DENSE_CSV) or .npy (DENSE_NPY, ``head`` its header) of a host CSR, rendered
+    on the GPU in bands and streamed to ``path``.  Returns the g2n_dense_info fields; ``declined`` = 1: nothing
+    was written (a row that is not sorted or holds a duplicate)."""
+    lib = load()
+    ip, ix, val, iw, code = _dense_args(indptr, indices, data, n_rows)
+    info = DenseInfo()
+    rc = lib.g2n_write_dense(os.fsencode(path), int(kind), head if head else None, len(head), ip.ctypes.data, _ptr(ix),
+                             iw, _ptr(val), code, n_rows, n_cols, int(band_bytes), int(device), ctypes.byref(info))
+    if rc == E_IO:
+        raise _io_error(rc, path)
+    _raise_status(rc, "dense writer")
+    return _dense_info(info)
+
+
+def dense_last_times() -> dict:
+    """g2n_dense_last_times: where this thread's last write_dense spent its time (ms; render and copy are sums
+    over the bands, which overlap each other and the writes)."""
+    out = (ctypes.c_double * 5)()
+    load().g2n_dense_last_times(ctypes.byref(out))
+    return dict(zip(("plan_ms", "render_ms", "copy_ms", "write_ms", "total_ms"), (float(x) for x in out)))
+
+
+def dense_range(kind: int, indptr: np.ndarray, indices: np.ndarray, data: np.ndarray, n_rows: int, n_cols: int,
+                b0: int, b1: int, device: int = 0) -> tuple[bytes | None, dict]:
+    """g2n_dense_range: bytes [b0, b1) of the same document's body (None when the writer declines) and the
+    g2n_dense_info fields."""
+    lib = load()
+    ip, ix, val, iw, code = _dense_args(indptr, indices, data, n_rows)
+    if b0 < 0 or b1 < b0:
+        raise ValueError("GPU dense range: 0 <= b0 <= b1")
+    out = np.empty(b1 - b0, dtype=np.uint8)
+    info = DenseInfo()
+    rc = lib.g2n_dense_range(int(kind), ip.ctypes.data, _ptr(ix), iw, _ptr(val), code, n_rows, n_cols, int(device),
+                             b0, b1, _ptr(out), ctypes.byref(info))
+    _raise_status(rc, "dense range")
+    d = _dense_info(info)
+    return (None if d["declined"] else out.tobytes()), d
 
 
 def device_count() -> int:

@@ -39,7 +39,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "export_edge_list", "export_graph_json", "export_graph_gexf", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
+           "save_npz", "write_dense", "dense_range", "export_edge_list", "export_graph_json", "export_graph_gexf", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
            "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
@@ -1641,6 +1641,8 @@ def save_matrix(A, dest: Path, *, verbose: bool = False, max_dense_gb: float = 5
             print(msg, "...", end="", file=sys.stderr, flush=True)
     if dest.suffix == ".npz":
         save_npz(dest, A)
+    elif dest.suffix in {".npy", ".csv"} and _dense_native(A) and not write_dense(A, dest, return_info=True)["declined"]:
+        pass  # rendered from the CSR on the GPU: the same bytes, no dense array
     elif dest.suffix == ".npy":
         np.save(dest, A.toarray() if sp.issparse(A) else A)
     elif dest.suffix == ".csv":
@@ -1653,6 +1655,90 @@ def save_matrix(A, dest: Path, *, verbose: bool = False, max_dense_gb: float = 5
             bar.close()
         else:
             print(f" done in {time.perf_counter() - start:,.1f}s", file=sys.stderr)
+
+
+def _dense_native(A) -> bool:
+    """Whether save_matrix renders A's dense .csv / .npy on the GPU: a scipy CSR or CSC of one of the five native
+    dtypes with no empty dimension, and a device to run on.  Everything else — COO and DOK (whose toarray() sums
+    duplicates in an order that is scipy's), ndarray and DataFrame, other dtypes, empty shapes, no GPU — is
+    numpy's, as in the reference."""
+    return (sp.issparse(A) and A.format in ("csr", "csc") and len(A.shape) == 2 and min(A.shape) >= 1
+            and np.dtype(A.dtype).name in nat.DTYPE_CODES and nat.device_count() > 0)
+
+
+_DENSE_KINDS = {".csv": nat.DENSE_CSV, "csv": nat.DENSE_CSV, nat.DENSE_CSV: nat.DENSE_CSV,
+                ".npy": nat.DENSE_NPY, "npy": nat.DENSE_NPY, nat.DENSE_NPY: nat.DENSE_NPY}
+
+
+def _dense_csr(A, device: int, kind: int):
+    """A's CSR arrays for the dense writers, as (indptr, indices, data, rows, columns of the array they describe).
+    A CSC's csv goes through the native COO -> CSR (a canonical CSC holds no duplicates, so nothing is added); its
+    .npy needs no conversion: csc.toarray() is Fortran-ordered, so the body is the C-order array of the transpose,
+    whose CSR the CSC's own arrays are.  Index arrays of other or mixed dtypes are widened to int64."""
+    if not sp.issparse(A) or A.format not in ("csr", "csc") or len(A.shape) != 2:
+        raise TypeError("the GPU dense writers take a scipy sparse CSR or CSC matrix")
+    if np.dtype(A.dtype).name not in nat.DTYPE_CODES:
+        raise NotImplementedError(f"GPU dense writers support {sorted(nat.DTYPE_CODES)}, not {A.dtype}")
+    if min(A.shape) < 1:
+        raise ValueError("the GPU dense writers take a matrix without an empty dimension")
+    n_rows, n_cols = int(A.shape[0]), int(A.shape[1])
+    if A.format == "csc":
+        if kind == nat.DENSE_NPY:
+            n_rows, n_cols = n_cols, n_rows
+        else:
+            A = _native_tocsr(A.tocoo(), device)
+    indptr, indices = A.indptr, A.indices
+    if indptr.dtype != indices.dtype or indptr.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        indptr, indices = indptr.astype(np.int64), indices.astype(np.int64)
+    return indptr, indices, A.data, n_rows, n_cols
+
+
+def write_dense(A, dest, *, device: int = 0, band_bytes: int | None = None, return_info: bool = False):
+    """``np.savetxt(dest, A.toarray(), delimiter=",", fmt="%.6g")`` (dest ending in .csv) or ``np.save(dest,
+    A.toarray())`` (.npy) of a scipy CSR / CSC matrix, byte for byte, without the dense array: the document is
+    rendered on the GPU in bands of ``band_bytes`` and streamed to the file (g2n_write_dense).  The info dict
+    (``return_info``) holds doc_bytes, bands, tile_bytes, band_bytes and declined; declined = 1 means nothing was
+    written — a row that is not sorted or holds a duplicate, which numpy's route adds up in scipy's order.
+    There is no CPU route here: without a GPU the call raises."""
+    dest = Path(dest)
+    if dest.suffix not in (".csv", ".npy"):
+        raise ValueError("a dense matrix path must end with .npy or .csv")
+    kind = _DENSE_KINDS[dest.suffix]
+    indptr, indices, data, n_rows, n_cols = _dense_csr(A, device, kind)
+    # (an array with one row or one column is C-contiguous whatever its order: numpy's header says so)
+    fortran = A.format == "csc" and min(A.shape) > 1
+    head = _npy_header_of(A.shape, data.dtype, fortran) if kind == nat.DENSE_NPY else b""
+    with open(dest, "wb" if kind == nat.DENSE_NPY else "w"):  # numpy's own open: the same OSError cases
+        pass
+    info = nat.write_dense(os.fspath(dest), kind, head, indptr, indices, data, n_rows, n_cols,
+                           band_bytes=band_bytes or 0, device=device)
+    return info if return_info else None
+
+
+def dense_range(A, kind, b0: int, b1: int, *, device: int = 0) -> bytes:
+    """Bytes [b0, b1) of the body of the document write_dense writes for A (``kind``: "csv" or "npy"; the .npy
+    body follows its header; a CSC's is Fortran-ordered, as csc.toarray() is): any place of a document too large to
+    write (g2n_dense_range)."""
+    if kind not in _DENSE_KINDS:
+        raise ValueError('kind must be "csv" or "npy"')
+    indptr, indices, data, n_rows, n_cols = _dense_csr(A, device, _DENSE_KINDS[kind])
+    out, _info = nat.dense_range(_DENSE_KINDS[kind], indptr, indices, data, n_rows, n_cols, int(b0), int(b1),
+                                 device=device)
+    if out is None:
+        raise ValueError("GPU dense range: a row of the matrix is not sorted or holds a duplicate")
+    return out
+
+
+def _npy_header_of(shape: tuple, dtype, fortran_order: bool = False) -> bytes:
+    """The .npy header of an array of this shape, dtype and order (numpy's own format code)."""
+    import io
+
+    from numpy.lib import format as npf
+
+    bio = io.BytesIO()
+    npf._write_array_header(bio, {"shape": tuple(int(x) for x in shape), "fortran_order": bool(fortran_order),
+                                  "descr": npf.dtype_to_descr(np.dtype(dtype))}, None)
+    return bio.getvalue()
 
 
 def _npy_header(val: np.ndarray) -> bytes:

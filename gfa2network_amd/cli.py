@@ -3,7 +3,9 @@
 Same global flags (they precede the subcommand) and ``convert`` flags as
 gfa2network/cli.py:22-135, same handler order (cli.py:193-250): print the backend, parse,
 ``convert_format``, ``save_matrix`` (dense guard -> SystemExit), then the
-``<matrix>.nodes.tsv`` sidecar.  ``export --format edge-list`` (cli.py:264-281) renders its
+``<matrix>.nodes.tsv`` sidecar.  ``--matrix x.csv`` and ``x.npy`` of the CSR or CSC a build returns are rendered
+on the GPU from the sparse matrix (``write_dense``: numpy's bytes, no dense array; the five ``--dtype`` choices,
+rows without duplicates); ``--matrix-format coo|dok`` keeps numpy's ``toarray()`` route.  ``export --format edge-list`` (cli.py:264-281) renders its
 lines on the GPU from the same parse, ``export --format json`` (cli.py:282-306) the graph's node-link
 document (``export_graph_json``), ``export --format gexf`` (cli.py:296-297) its GEXF document
 (``export_graph_gexf``); ``stats`` (cli.py:152-159, 364-376) prints

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "g2n_internal.h"
+#include "g6fmt.h"
 
 namespace g2n {
 
@@ -759,6 +760,8 @@ int64_t g2n_first_bad_utf8(const uint8_t* blob, const int64_t* offsets, uint64_t
     return -1;
   }
 }
+
+uint32_t g2n_format_g6(double v, uint8_t out[16]) { return g2n::g6_format(v, out); }
 
 void g2n_result_free(g2n_result* r) {
   if (!r) return;

@@ -8,6 +8,9 @@
 // (scans), g2n_sort.hip (stable radix sort), g2n_sym.hip (bucket partition), g2n_route.hip.  Counts are read back between phases (a few
 // small synchronous copies per build) to size the next phase's buffers exactly.
 #include <hip/hip_runtime.h>
+#include <errno.h>
+#include <fcntl.h>
+#include <unistd.h>
 
 #include <chrono>
 #include <cstring>
@@ -15,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 #include "g2n_internal.h"
 #include "g2n_kernels.hip"
@@ -56,6 +60,7 @@ enum Slot {
   S_GJKEY, S_GJBCNT, S_GJBOFF, S_GJSTART, S_GJORI, S_GJCR, S_GJCC, S_GJIDX, S_GJK1, S_GJIDX1, S_GJK2, S_GJRS, S_GJPERM,
   S_GJHEAD, S_GJHX, S_GJHS, S_GJFFLAG, S_GJFX, S_GJFGRP, S_GJLRS, S_GJORDER, S_GJCNT, S_GJBASE, S_GJGBASE, S_GJLS, S_GJLT,
   S_GJLX, S_GJHEADSTR,  // G2N_OUT_GRAPH_JSON (g2n_graphjson.hip), G2N_OUT_GRAPH_GEXF (g2n_graphgexf.hip)
+  S_DNIP, S_DNIX, S_DNVAL, S_DNFLAG, S_DNSLOT, S_DNEXTRA, S_DNX, S_DNBAND0, S_DNBAND1,  // g2n_write_dense / g2n_dense_range (g2n_dense.hip)
   S_QSTATE, S_QLINES, S_QNODE, S_QFPOS, S_QFLAG, S_QLAST, S_QCAND, S_QIDS, S_QBYTES, S_QNLEN, S_QNOFF, S_QNBLOB,  // g2n_seq_distance_from_path (g2n_seq.hip)
   S_NSLOTS
 };
@@ -2407,6 +2412,8 @@ static void download_result(g2n_context* c, const g2n_result& D, HostResult* H) 
 
 // the queries over a finished CSR (stats, path distances) and the results of the host builds that ask for one
 #include "g2n_queries.hip"
+// convert --matrix x.csv / x.npy: the dense documents of a CSR, rendered in byte ranges
+#include "g2n_dense.hip"
 
 namespace g2n {
 
@@ -3379,6 +3386,34 @@ int g2n_csr_pair_distances_weighted_host(const void* indptr, const void* indices
   return g2n::guarded([&] {
     return g2n::csr_pair_distances_weighted_host(indptr, indices, index_width, values, n, nnz, sources, n_src, targets,
                                                  n_tgt, out, device, info);
+  });
+}
+
+int g2n_write_dense(const char* path, int32_t kind, const void* head, size_t head_len, const void* indptr,
+                    const void* indices, int32_t index_width, const void* data, int32_t dtype, uint64_t n_rows,
+                    uint64_t n_cols, uint64_t band_bytes, int32_t device, g2n_dense_info* info) {
+  if (!path || !info || (head_len && !head)) return G2N_E_ARG;
+  std::memset(info, 0, sizeof(*info));
+  return g2n::guarded([&] {
+    const uint64_t nnz = g2n::dense_host_nnz("g2n_write_dense", indptr, index_width, n_rows);
+    return g2n::write_dense(path, kind, head, head_len, indptr, indices, index_width, data, dtype, n_rows, n_cols, nnz,
+                            band_bytes, device, info);
+  });
+}
+
+void g2n_dense_last_times(double out_ms[5]) {
+  if (out_ms) g2n::dense_last_times(out_ms);
+}
+
+int g2n_dense_range(int32_t kind, const void* indptr, const void* indices, int32_t index_width, const void* data,
+                    int32_t dtype, uint64_t n_rows, uint64_t n_cols, int32_t device, uint64_t b0, uint64_t b1,
+                    uint8_t* out, g2n_dense_info* info) {
+  if (!info) return G2N_E_ARG;
+  std::memset(info, 0, sizeof(*info));
+  return g2n::guarded([&] {
+    const uint64_t nnz = g2n::dense_host_nnz("g2n_dense_range", indptr, index_width, n_rows);
+    return g2n::dense_range(kind, indptr, indices, index_width, data, dtype, n_rows, n_cols, nnz, device, b0, b1, out,
+                            info);
   });
 }
 

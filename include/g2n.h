@@ -330,6 +330,47 @@ int g2n_write_node_map(const char *path, const uint8_t *blob, const int64_t *off
 /* Index of the first name that is not valid UTF-8 (Python's strict decoder), or -1. */
 int64_t g2n_first_bad_utf8(const uint8_t *blob, const int64_t *offsets, uint64_t n_names);
 
+/* ---- convert CLI dense writers (GPU) ------------------------------------------------------
+ * `convert --matrix x.csv` / `x.npy` (utils.py:87-96): np.savetxt(dest, A.toarray(), delimiter=",",
+ * fmt="%.6g") and np.save(dest, A.toarray()) of a CSR matrix, byte for byte, without the dense array:
+ * the document is rendered on the device in bands of band_bytes (g2n_dense.hip) and streamed to the
+ * file — a band renders while the one before it is copied to pinned host memory and the one before
+ * that is written.  The CSR is in HOST memory: indptr (n_rows + 1) / indices of index_width 4 or 8
+ * bytes, data of `dtype` (one of the five G2N_* codes), n_rows, n_cols >= 1 and < 2^31 - 1, fewer than
+ * 2^32 - 1 entries (else G2N_E_UNSUPPORTED); rows sorted and free of duplicates.  kind: 0 the csv, 1
+ * the .npy, whose header `head` (head_len bytes, built by the caller with numpy's format code; empty
+ * for the csv) is written first.  band_bytes: 0 = sized from the device's free memory, else a multiple
+ * of info->tile_bytes.  info: doc_bytes = the bytes of the body (the file holds head_len more), bands,
+ * tile_bytes = the aligned tile of the csv one render block writes, band_bytes = the band used.
+ * declined = 1 (status G2N_OK, the file not touched): a row whose columns do not ascend strictly —
+ * numpy's toarray() adds duplicates in an order that is scipy's, so the caller takes numpy's route.
+ * G2N_E_ARG for an indptr that is no non-decreasing map into [0, nnz] or a column outside [0, n_cols)
+ * (nothing out of range is ever addressed); G2N_E_IO, the errno's text in g2n_last_error, when the
+ * file cannot be opened or written.  Device memory: the CSR, 25 bytes per entry (csv) and two bands. */
+typedef struct g2n_dense_info {
+  uint64_t doc_bytes, bands, tile_bytes, band_bytes;
+  int32_t declined;
+} g2n_dense_info;
+int g2n_write_dense(const char *path, int32_t kind /* 0 csv, 1 npy */, const void *head, size_t head_len,
+                    const void *indptr, const void *indices, int32_t index_width, const void *data, int32_t dtype,
+                    uint64_t n_rows, uint64_t n_cols, uint64_t band_bytes /* 0 = default */, int32_t device,
+                    g2n_dense_info *info);
+/* Where the calling thread's last g2n_write_dense spent its time, in ms: out_ms[0] the upload of the
+ * CSR with D1 and the scan (host clock), [1] the bands' renders and [2] their copies to the host
+ * (hipEvent, summed over the bands: they overlap each other and the writes), [3] the write(2) calls
+ * (host clock), [4] the whole call. */
+void g2n_dense_last_times(double out_ms[5]);
+/* Bytes [b0, b1) of the same document's body (b0 <= b1 <= info->doc_bytes, else G2N_E_ARG) to out
+ * (host, b1 - b0 bytes): what the band loop renders, for any place of a document too large to write.
+ * info as above with bands = band_bytes = 0; declined = 1 leaves out unwritten. */
+int g2n_dense_range(int32_t kind, const void *indptr, const void *indices, int32_t index_width, const void *data,
+                    int32_t dtype, uint64_t n_rows, uint64_t n_cols, int32_t device, uint64_t b0, uint64_t b1,
+                    uint8_t *out, g2n_dense_info *info);
+/* Python's '%.6g' % v (what np.savetxt writes per cell; csrc/g6fmt.h, the code the device runs): the
+ * text into out[0 .. length), at most 13 bytes, out[15] = the length, the bytes between zero.  Returns
+ * the length.  Exact for every double: 6 significant digits, ties to even on the binary value. */
+uint32_t g2n_format_g6(double v, uint8_t out[16]);
+
 /* convert_format(A, "csr") for a COO matrix (utils.py:40-63 -> scipy coo.tocsr):
  * sums duplicates in dtype with scipy's summation order, keeps explicit zeros.
  * rows/cols have index_width (4) bytes per element, data has dtype elements; n_rows x n_cols
