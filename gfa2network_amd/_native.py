@@ -42,6 +42,8 @@ EXPORTED = [
     "g2n_keyset_create", "g2n_keyset_add", "g2n_keyset_view", "g2n_keyset_free",
     "g2n_gunzip", "g2n_gunzip_chunked", "g2n_free", "g2n_split_render", "g2n_split_get", "g2n_split_segments", "g2n_split_free", "g2n_join_names", "g2n_gather_names", "g2n_write_npz", "g2n_write_node_map", "g2n_first_bad_utf8",
     "g2n_csr_stats", "g2n_csr_stats_host", "g2n_stats_from_path",
+    "g2n_csr_components", "g2n_csr_components_host", "g2n_csr_split_components_host", "g2n_components_from_path",
+    "g2n_write_node_labels",
     "g2n_csr_path_distances", "g2n_csr_path_distances_host", "g2n_load_paths", "g2n_paths_get", "g2n_paths_free",
     "g2n_distances_from_path", "g2n_csr_path_distances_weighted", "g2n_csr_path_distances_weighted_host",
     "g2n_seq_distance_from_path", "g2n_seq_hits_get", "g2n_seq_hits_names", "g2n_seq_hits_free",
@@ -155,6 +157,22 @@ class GraphStats(ctypes.Structure):
         ("ms_degree", ctypes.c_double),
         ("ms_components", ctypes.c_double),
     ]
+
+
+class ComponentsInfo(ctypes.Structure):
+    """g2n_components_info (include/g2n.h)."""
+
+    _fields_ = [
+        ("n_components", ctypes.c_int64),
+        ("ms_union", ctypes.c_double),
+        ("ms_labels", ctypes.c_double),
+        ("ms_group", ctypes.c_double),
+        ("ms_split", ctypes.c_double),
+    ]
+
+
+SPLIT_SHORT_ROW = 64  # kSplitShortRow (csrc/g2n_components.hip): longer rows are copied by a block each ...
+SPLIT_HUGE_ROW = 4096  # kSplitHugeRow: ... and rows longer than this by the whole grid
 
 
 class DistInfo(ctypes.Structure):
@@ -391,6 +409,18 @@ def load() -> ctypes.CDLL:
     lib.g2n_stats_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), ctypes.POINTER(GraphStats),
                                         ctypes.POINTER(I64), ctypes.POINTER(ctypes.POINTER(Result))]
     lib.g2n_stats_from_path.restype = ctypes.c_int
+    CI = ctypes.POINTER(ComponentsInfo)
+    lib.g2n_csr_components.argtypes = [P, P, P, I32, U64, U64, P, CI]
+    lib.g2n_csr_components.restype = ctypes.c_int
+    lib.g2n_csr_components_host.argtypes = [P, P, I32, U64, U64, P, I32, CI]
+    lib.g2n_csr_components_host.restype = ctypes.c_int
+    lib.g2n_csr_split_components_host.argtypes = [P, P, P, I32, I32, U64, U64, P, P, P, P, P, P, I32, CI]
+    lib.g2n_csr_split_components_host.restype = ctypes.c_int
+    lib.g2n_components_from_path.argtypes = [ctypes.c_char_p, ctypes.POINTER(Options), CI,
+                                             ctypes.POINTER(ctypes.POINTER(Result))]
+    lib.g2n_components_from_path.restype = ctypes.c_int
+    lib.g2n_write_node_labels.argtypes = [ctypes.c_char_p, P, P, P, U64, I32, ctypes.POINTER(I64)]
+    lib.g2n_write_node_labels.restype = ctypes.c_int
     lib.g2n_csr_path_distances.argtypes = [P, P, P, I32, U64, U64, P, P, U64, I32, P, ctypes.POINTER(DistInfo)]
     lib.g2n_csr_path_distances.restype = ctypes.c_int
     lib.g2n_csr_path_distances_host.argtypes = [P, P, I32, U64, U64, P, P, U64, I32, P, I32, ctypes.POINTER(DistInfo)]
@@ -700,6 +730,59 @@ def csr_stats_host(indptr: np.ndarray, indices: np.ndarray, n: int, directed: bo
                                 ctypes.byref(st))
     _raise_status(rc, "graph statistics")
     return _stats_dict(st)
+
+
+def _components_info(info: ComponentsInfo) -> dict:
+    return {"n_components": int(info.n_components), "ms_union": float(info.ms_union),
+            "ms_labels": float(info.ms_labels), "ms_group": float(info.ms_group), "ms_split": float(info.ms_split)}
+
+
+def csr_components_host(indptr: np.ndarray, indices: np.ndarray, n: int, device: int = 0):
+    """g2n_csr_components_host on a host CSR's structure: (int32 labels, the g2n_components_info fields)."""
+    lib = load()
+    ip, ix, _val, idt = _csr_args(indptr, indices, n)
+    labels = np.empty(n, dtype=np.int32)
+    info = ComponentsInfo()
+    rc = lib.g2n_csr_components_host(ip.ctypes.data, _ptr(ix), idt.itemsize, n, len(ix), _ptr(labels), int(device),
+                                     ctypes.byref(info))
+    _raise_status(rc, "components")
+    return labels, _components_info(info)
+
+
+def csr_split_components_host(indptr: np.ndarray, indices: np.ndarray, data, n: int, device: int = 0):
+    """g2n_csr_split_components_host: (labels, perm, offsets of the k + 1 component bounds, out_indptr,
+    out_indices, out_data or None, info).  data: None, or one item of 1, 4 or 8 bytes per index (copied
+    as bits; the result has its dtype)."""
+    lib = load()
+    ip, ix, _val, idt = _csr_args(indptr, indices, n)
+    val = None if data is None else np.ascontiguousarray(data)
+    vb = 0 if val is None else val.dtype.itemsize
+    if val is not None and (vb not in (1, 4, 8) or len(val) != len(ix)):
+        raise ValueError("data must hold one item of 1, 4 or 8 bytes per index")
+    labels, perm, off = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int64), np.empty(n + 1, dtype=np.int64)
+    oip, oix = np.empty(n + 1, dtype=idt), np.empty(len(ix), dtype=idt)
+    oval = None if val is None else np.empty(len(ix), dtype=val.dtype)
+    info = ComponentsInfo()
+    rc = lib.g2n_csr_split_components_host(ip.ctypes.data, _ptr(ix), None if val is None else _ptr(val), vb,
+                                           idt.itemsize, n, len(ix), _ptr(labels), _ptr(perm), off.ctypes.data,
+                                           oip.ctypes.data, _ptr(oix), None if oval is None else _ptr(oval),
+                                           int(device), ctypes.byref(info))
+    _raise_status(rc, "components")
+    return labels, perm, off[:int(info.n_components) + 1].copy(), oip, oix, oval, _components_info(info)
+
+
+def components_from_path(path: str, opts: Options):
+    """g2n_components_from_path: (the build's result — names, no matrix —, int32 labels, the
+    g2n_components_info fields).  Labels are meaningful only when the result's status is OK."""
+    lib = load()
+    res = ctypes.POINTER(Result)()
+    info = ComponentsInfo()
+    rc = lib.g2n_components_from_path(os.fsencode(path), ctypes.byref(opts), ctypes.byref(info), ctypes.byref(res))
+    labels = np.zeros(0, dtype=np.int32)
+    if res and res.contents.status == OK and res.contents.rows and res.contents.n_nodes:
+        labels = np.ctypeslib.as_array(ctypes.cast(res.contents.rows, ctypes.POINTER(ctypes.c_int32)),
+                                       shape=(res.contents.n_nodes,)).copy()
+    return _from_result(res, rc), labels, _components_info(info)
 
 
 def csr_path_distances_host(indptr: np.ndarray, indices: np.ndarray, n: int, path_ptr: np.ndarray,
@@ -1241,6 +1324,20 @@ def write_node_map(path: str, blob: np.ndarray, offsets: np.ndarray, check_utf8:
     bad = ctypes.c_int64(-1)
     rc = lib.g2n_write_node_map(os.fsencode(path), blob.ctypes.data if blob.size else None,
                                 offsets.ctypes.data, max(n, 0), int(check_utf8), ctypes.byref(bad))
+    if rc != OK:
+        raise _io_error(rc, path)
+    return int(bad.value)
+
+
+def write_node_labels(path: str, blob: np.ndarray, offsets: np.ndarray, labels: np.ndarray, check_utf8: bool) -> int:
+    """``name\\tlabel\\n`` per node from the names blob (g2n_write_node_labels; path "-": standard
+    output); returns the first id whose name is not UTF-8 (only the lines before it were written), or -1."""
+    lib = load()
+    n = len(labels)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    bad = ctypes.c_int64(-1)
+    rc = lib.g2n_write_node_labels(os.fsencode(path), _ptr(blob), offsets.ctypes.data if n else None, _ptr(lab), n,
+                                   int(check_utf8), ctypes.byref(bad))
     if rc != OK:
         raise _io_error(rc, path)
     return int(bad.value)

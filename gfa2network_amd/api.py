@@ -18,6 +18,7 @@ import gzip
 import io
 import os
 import sys
+import tempfile
 import time
 import warnings
 import zlib
@@ -39,7 +40,7 @@ except Exception:  # noqa: BLE001 - the same broad guard as the reference
     _HAS_TQDM = False
 
 __all__ = ["parse_gfa", "parse_gfa_names", "parse_gfa_sharded", "convert_format", "finalize", "raise_for_status",
-           "save_npz", "write_dense", "dense_range", "export_edge_list", "export_graph_json", "export_graph_gexf", "compute_stats", "graph_stats", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
+           "save_npz", "write_dense", "dense_range", "export_edge_list", "export_graph_json", "export_graph_gexf", "compute_stats", "graph_stats", "graph_components", "split_components", "node_components", "write_node_components", "ComponentSplit", "density", "path_distances", "min_table", "mean_table", "weighted_min_table", "weighted_mean_table", "weighted_fold_table", "graph_matrix", "load_paths", "genome_distance", "genome_distance_matrix",
            "sequence_distance", "sequence_nodes", "NodeNotFound", "NetworkXNoPath"]
 
 # Auto-sharding (BASELINE north_star: byte-range-shard "only when it exceeds one GPU's HBM"): a
@@ -774,6 +775,96 @@ def graph_stats(A, *, directed: bool = True, device: int = 0) -> dict:
             "max_degree": st["max_degree"], "density": density(st["n_nodes"], edges, directed)}
 
 
+_NATIVE_DTYPES = tuple(np.dtype(k) for k in nat.DTYPE_CODES)
+
+
+def _components_csr(A, who: str, structure_only: bool):
+    """The square scipy sparse matrix ``A`` as the component calls take it: (n, indptr, indices — both
+    int32 or both int64, the stored entries only —, the CSR itself)."""
+    if not sp.issparse(A):
+        raise TypeError(f"{who} takes a scipy sparse matrix")
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"{who} takes a square matrix")
+    if A.format != "csr":
+        if structure_only:  # unit values in a dtype whose sums cannot overflow, as graph_stats
+            C = A.tocoo()
+            A = sp.coo_matrix((np.ones(C.nnz, dtype=np.float64), (C.row, C.col)), shape=C.shape).tocsr()
+        else:
+            A = A.tocsr()
+    n = int(A.shape[0])
+    if n >= 2**31 - 1:
+        raise NotImplementedError("GPU components need node ids below 2^31 - 1")
+    idt = np.int64 if np.dtype(A.indptr.dtype) == np.int64 or np.dtype(A.indices.dtype) == np.int64 else np.int32
+    nnz = int(A.indptr[-1]) if n else 0
+    return n, np.asarray(A.indptr, dtype=idt), np.asarray(A.indices[:nnz], dtype=idt), A
+
+
+def graph_components(A, *, device: int = 0):
+    """``(n_components, labels)`` of the graph whose adjacency structure is the square scipy sparse
+    matrix ``A`` (extension; the counterpart of ``graph_stats``): every stored (u, v) joins u and v, the
+    values are never read.  ``labels`` is an int32 array, equal to
+    ``scipy.sparse.csgraph.connected_components(A, directed=False)``'s: components are numbered by
+    their smallest node.  Runs on the GPU (g2n_csr_components_host); there is no CPU route."""
+    n, ip, ix, _ = _components_csr(A, "graph_components", True)
+    if n == 0:
+        return 0, np.zeros(0, dtype=np.int32)
+    labels, info = nat.csr_components_host(ip, ix, n, device)
+    return info["n_components"], labels
+
+
+class ComponentSplit:
+    """What ``split_components`` returns: ``n_components``, ``labels`` (int32, one per node), ``sizes``
+    (``np.bincount(labels)``), ``perm`` (the nodes ordered by label: ``np.argsort(labels,
+    kind="stable")``) and ``offsets`` (component j's nodes are ``perm[offsets[j]:offsets[j + 1]]``), over
+    the whole matrix regrouped by component on the GPU (``indptr`` / ``indices`` / ``data``: row p is
+    row ``perm[p]`` of the input, its columns local to its component)."""
+
+    def __init__(self, shape_dtype, labels, perm, offsets, indptr, indices, data, info=None):
+        self.dtype = np.dtype(shape_dtype)
+        self.labels, self.perm, self.offsets = labels, perm, offsets
+        self.indptr, self.indices, self.data = indptr, indices, data
+        self.n_components = len(offsets) - 1
+        self.sizes = np.diff(offsets)
+        self.info = info or {}
+
+    def component(self, j: int):
+        """``(A_j, nodes_j)``: component j as a CSR matrix of the input's dtype and the nodes it holds
+        (ascending; ``np.flatnonzero(labels == j)``).  Each row keeps its entries in stored order: for a
+        canonical input ``A_j`` has the arrays of ``A[nodes_j][:, nodes_j]``."""
+        j = int(j)
+        if not 0 <= j < self.n_components:
+            raise IndexError(f"component {j} of {self.n_components}")
+        lo, hi = int(self.offsets[j]), int(self.offsets[j + 1])
+        ip = self.indptr[lo:hi + 1]
+        b, e = int(ip[0]), int(ip[-1])
+        A = sp.csr_matrix((self.data[b:e], self.indices[b:e], ip - ip[0]), shape=(hi - lo, hi - lo), dtype=self.dtype,
+                          copy=False)
+        return A, self.perm[lo:hi]
+
+    def largest(self):
+        """``component(j)`` of the largest component, the lowest label on ties."""
+        return self.component(int(np.argmax(self.sizes)))
+
+
+def split_components(A, *, device: int = 0) -> ComponentSplit:
+    """The connected components of the square scipy sparse matrix ``A`` as matrices of their own
+    (extension): labels as ``graph_components``, and the matrix regrouped by component on the GPU
+    (g2n_csr_split_components_host) so that ``component(j)`` is a slice.  ``A``'s dtype is one of the
+    five native ones; a matrix in another format goes through ``A.tocsr()`` first."""
+    if sp.issparse(A) and np.dtype(A.dtype) not in _NATIVE_DTYPES:
+        raise NotImplementedError(f"split_components: dtype {A.dtype} is not one of bool, int8, int32, float32, float64")
+    n, ip, ix, A = _components_csr(A, "split_components", False)
+    dt = np.dtype(A.dtype)
+    if n == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return ComponentSplit(dt, np.zeros(0, dtype=np.int32), z, np.zeros(1, dtype=np.int64),
+                              np.zeros(1, dtype=ip.dtype), np.zeros(0, dtype=ip.dtype), np.zeros(0, dtype=dt))
+    data = np.ascontiguousarray(A.data[:len(ix)])
+    bits = data.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[dt.itemsize])
+    labels, perm, off, oip, oix, oval, info = nat.csr_split_components_host(ip, ix, bits, n, device)
+    return ComponentSplit(dt, labels, perm, off, oip, oix, oval.view(dt), info)
+
+
 def min_table(D: np.ndarray) -> np.ndarray:
     """The directed float64 table of g2n_csr_path_distances' uint32 ``D``: ``M[i][j]`` = the fewest
     hops from a step of path i to a step of path j, ``inf`` where none is reached (0xFFFFFFFF), 0.0
@@ -990,25 +1081,103 @@ def compute_stats(path, *, directed: bool = True, strip_orientation: bool = Fals
     CSR is built in HBM, the statistics are taken from it there (g2n_stats.hip) and only scalars come
     back.  Stdin and file objects raise NotImplementedError (the reference reads its input twice, so a
     pipe gives it no paths).  ``device`` is an extension."""
-    if hasattr(path, "read") or str(path) == "-":
-        raise NotImplementedError("compute_stats reads a named file (the reference parses its input twice)")
-    _stats_one_piece(path, device)
-    opts = nat.make_options(directed=directed, strip_orientation=strip_orientation, asymmetric=True,
-                            output=nat.OUT_CSR, want_node_names=not raw_bytes_id, device=device)
-    raw, st, n_paths = nat.stats_from_path(str(path), opts)
+    raw, st, n_paths = _plain_graph_pass(path, "compute_stats", directed, strip_orientation, raw_bytes_id, device,
+                                         nat.stats_from_path)
     dt = np.dtype("float64")
-    if raw.status == nat.E_UNICODE and raw.err_line < 0:
-        # builders.py:155-162: the graph path decodes every node key as ASCII (the parse itself was clean)
-        if raw.has_warning:
-            warnings.warn(f"Skipping unsupported record: {chr(raw.warn_byte)}", RuntimeWarning, stacklevel=2)
-        bytes(raw.err_detail).decode("ascii")
-        raise AssertionError("decode of the reported key unexpectedly succeeded")
     finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=raw_bytes_id, verbose=False, build_matrix=False,
              path=path)
     raise_for_status(raw, dt, path)
     edges = _stats_edges(st, directed)
     return {"nodes": st["n_nodes"], "edges": edges, "paths": n_paths, "components": st["n_components"],
             "max_degree": st["max_degree"], "density": density(st["n_nodes"], edges, directed)}
+
+
+def _plain_graph_pass(path, who: str, directed: bool, strip_orientation: bool, raw_bytes_id: bool, device: int, call):
+    """``call(path, opts)`` (stats_from_path / components_from_path) on the graph compute_stats
+    measures, with its named-file and one-piece rules and the graph path's ASCII decode of node keys;
+    returns what the call returned (the caller finalizes its result: the warning names its caller)."""
+    if hasattr(path, "read") or str(path) == "-":
+        raise NotImplementedError(f"{who} reads a named file (the reference parses its input twice)")
+    _stats_one_piece(path, device, who, "graph_stats" if call is nat.stats_from_path else "graph_components")
+    opts = nat.make_options(directed=directed, strip_orientation=strip_orientation, asymmetric=True,
+                            output=nat.OUT_CSR, want_node_names=not raw_bytes_id, device=device)
+    out = call(str(path), opts)
+    raw = out[0]
+    if raw.status == nat.E_UNICODE and raw.err_line < 0:
+        # builders.py:155-162: the graph path decodes every node key as ASCII (the parse itself was clean)
+        if raw.has_warning:
+            warnings.warn(f"Skipping unsupported record: {chr(raw.warn_byte)}", RuntimeWarning, stacklevel=3)
+        bytes(raw.err_detail).decode("ascii")
+        raise AssertionError("decode of the reported key unexpectedly succeeded")
+    return out
+
+
+def node_components(path, *, directed: bool = True, strip_orientation: bool = False, raw_bytes_id: bool = False,
+                    device: int = 0):
+    """``(nodes, labels)`` of the graph ``compute_stats`` measures (extension): the nodes in first-touch
+    order (``str``, or ``bytes`` with ``raw_bytes_id``) and each one's component as an int32 array,
+    numbered as ``enumerate(nx.connected_components(G.to_undirected()))`` numbers them on the
+    reference's graph.  The file is parsed once, the CSR stays in HBM and is labelled there
+    (g2n_components_from_path).  Exceptions, the warning and the named-file and one-piece rules are
+    ``compute_stats``'s."""
+    raw, labels, _info = _plain_graph_pass(path, "node_components", directed, strip_orientation, raw_bytes_id, device,
+                                           nat.components_from_path)
+    dt = np.dtype("float64")
+    finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=raw_bytes_id, verbose=False, build_matrix=False,
+             path=path)
+    raise_for_status(raw, dt, path)
+    return _node_list(raw, raw_bytes_id), labels
+
+
+def write_node_components(path, output="-", *, directed: bool = True, strip_orientation: bool = False,
+                          raw_bytes_id: bool = False, sizes: bool = False, device: int = 0) -> None:
+    """The ``components`` subcommand: ``node\\tcomponent\\n`` per node of ``node_components(path, ...)`` in
+    node order, or (``sizes``) ``component\\tsize\\n`` per component, to the file ``output`` or to
+    standard output (``"-"``).  The listing is written natively from the names blob, no Python list;
+    with ``raw_bytes_id`` names are decoded while writing, as ``save_node_map_native`` does."""
+    raw, labels, info = _plain_graph_pass(path, "components", directed, strip_orientation, raw_bytes_id, device,
+                                          nat.components_from_path)
+    dt = np.dtype("float64")
+    finalize(raw, dtype=dt, return_node_list=False, raw_bytes_id=raw_bytes_id, verbose=False, build_matrix=False,
+             path=path)
+    raise_for_status(raw, dt, path)
+    to_stdout = str(output) == "-"
+    if sizes:
+        text = "".join(f"{j}\t{c}\n" for j, c in enumerate(np.bincount(labels, minlength=info["n_components"])))
+        if to_stdout:
+            sys.stdout.write(text)
+        else:
+            Path(output).write_text(text)
+        return
+    blob = raw.names_blob if raw.names_blob is not None else np.zeros(0, dtype=np.uint8)
+    offs = raw.names_offsets if raw.names_offsets is not None else np.zeros(1, dtype=np.int64)
+    tmp = None
+    dest = str(output)
+    if to_stdout:
+        try:
+            direct = sys.stdout.fileno() == 1
+        except (AttributeError, OSError, ValueError):
+            direct = False
+        if direct:
+            sys.stdout.flush()
+        else:  # a replaced sys.stdout: through a file of the listing
+            fd, tmp = tempfile.mkstemp(suffix=".tsv")
+            os.close(fd)
+            dest = tmp
+    else:
+        with open(dest, "w"):  # the same OSError cases as Python's open(dest, "w")
+            pass
+    try:
+        bad = nat.write_node_labels(dest, blob, offs, labels, check_utf8=raw_bytes_id)
+        if tmp is not None:
+            with open(tmp, "rb") as fh:
+                sys.stdout.write(fh.read().decode())
+    finally:
+        if tmp is not None:
+            os.unlink(tmp)
+    if bad >= 0:
+        bytes(blob[offs[bad]:offs[bad + 1]]).decode()
+        raise AssertionError("decode of the reported name unexpectedly succeeded")
 
 
 try:  # networkx is imported only for the exception types the reference's callers catch

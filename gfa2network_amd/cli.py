@@ -32,12 +32,13 @@ from pathlib import Path
 
 from . import __version__
 from .api import (compute_stats, convert_format, export_edge_list, export_graph_gexf, export_graph_json, genome_distance, genome_distance_matrix, parse_gfa,
-                  parse_gfa_names, save_matrix, save_node_map_native, sequence_distance)
+                  parse_gfa_names, save_matrix, save_node_map_native, sequence_distance, write_node_components)
 
 
 def _parser(extensions: bool = False) -> argparse.ArgumentParser:
     """The reference's parser (its flags, nothing else below the global ``--device``); ``extensions``:
-    plus this build's own subcommand flags — ``distance --method`` — as ``main`` parses."""
+    plus this build's own subcommand flags and subcommands — ``distance --method``, ``components`` — as
+    ``main`` parses."""
     parser = argparse.ArgumentParser(prog="gfa2network")
     parser.add_argument("--version", action="version", version=f"gfa2network-amd {__version__}")
     parser.add_argument("--raw-bytes-id", action="store_true", help="Use raw bytes for node identifiers (legacy)")
@@ -101,6 +102,15 @@ def _parser(extensions: bool = False) -> argparse.ArgumentParser:
     p_dm.add_argument("--method", choices=["min", "mean"], default="min")
     p_dm.add_argument("--backend", choices=["networkx", "igraph"], default="networkx", help="Graph backend to use")
     p_dm.add_argument("--verbose", action="store_true")
+    if extensions:
+        p_cc = sub.add_parser("components", help="List each node's connected component (GPU build option)")
+        p_cc.add_argument("gfa", help="Input *.gfa* file")
+        p_cc.add_argument("-o", "--output", metavar="PATH", default="-", help="Write the listing to PATH (default: stdout)")
+        g5 = p_cc.add_mutually_exclusive_group()
+        g5.add_argument("--directed", dest="directed", action="store_true", default=True)
+        g5.add_argument("--undirected", dest="directed", action="store_false")
+        p_cc.add_argument("--strip-orientation", action="store_true")
+        p_cc.add_argument("--sizes", action="store_true", help="Print component<TAB>size per component instead")
     return parser
 
 
@@ -134,6 +144,10 @@ def main(argv: list[str] | None = None) -> None:
         print("density\t", f"{stats['density']:.6g}")
         return
     if args.cmd == "stat":
+        return
+    if args.cmd == "components":  # (extension) node<TAB>component per node of the graph stats measures
+        write_node_components(args.gfa, args.output, directed=args.directed, strip_orientation=args.strip_orientation,
+                              raw_bytes_id=args.raw_bytes_id, sizes=args.sizes, device=args.device)
         return
     if args.cmd == "distance":  # cli.py:307-346
         if args.backend == "igraph":

@@ -330,6 +330,22 @@ int g2n_graph_gexf_from_buffer(const void* buf, size_t len, const g2n_options* o
   return g2n::guarded([&] { return g2n::build_host(buf, len, &scope.o, out, 0.0); });
 }
 
+// the plain graph's build of the stats and labels calls: the summed asymmetric CSR, whose values nobody reads
+static g2n_options plain_graph_opts(const g2n_options* opts, bool names) {
+  g2n_options o;
+  g2n_options_init(&o);
+  o.directed = opts->directed != 0;
+  o.strip_orientation = opts->strip_orientation != 0;
+  o.asymmetric = 1;
+  o.dtype = G2N_BOOL;
+  o.output = G2N_OUT_CSR;
+  o.want_node_names = names;
+  o.device = opts->device;
+  o.unknown_warned = opts->unknown_warned;
+  o.test_flags = opts->test_flags;
+  return o;
+}
+
 int g2n_stats_from_path(const char* path, const g2n_options* opts, g2n_graph_stats* stats, int64_t* n_paths,
                         g2n_result** res) {
   if (!res || !path || !stats || !n_paths) return G2N_E_ARG;
@@ -338,21 +354,26 @@ int g2n_stats_from_path(const char* path, const g2n_options* opts, g2n_graph_sta
   if (rc) return rc;
   std::memset(stats, 0, sizeof(*stats));
   *n_paths = 0;
-  g2n_options o;  // the plain graph's build: the summed asymmetric CSR, whose values nobody reads
-  g2n_options_init(&o);
-  o.directed = opts->directed != 0;
-  o.strip_orientation = opts->strip_orientation != 0;
-  o.asymmetric = 1;
-  o.dtype = G2N_BOOL;
-  o.output = G2N_OUT_CSR;
-  o.want_node_names = opts->want_node_names != 0;
-  o.device = opts->device;
-  o.unknown_warned = opts->unknown_warned;
-  o.test_flags = opts->test_flags;
+  const g2n_options o = plain_graph_opts(opts, opts->want_node_names != 0);
   const g2n::StatsRequest req{stats, n_paths, o.directed, o.want_node_names != 0};
   struct Scope {
     explicit Scope(const g2n::StatsRequest* r) { g2n::set_stats_request(r); }
     ~Scope() { g2n::set_stats_request(nullptr); }
+  } scope(&req);
+  return build_from_path(path, &o, res);
+}
+
+int g2n_components_from_path(const char* path, const g2n_options* opts, g2n_components_info* info, g2n_result** res) {
+  if (!res || !path || !info) return G2N_E_ARG;
+  *res = nullptr;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  std::memset(info, 0, sizeof(*info));
+  const g2n_options o = plain_graph_opts(opts, true);  // the names come back whatever the key check
+  const g2n::LabelsRequest req{info, opts->want_node_names != 0};
+  struct Scope {
+    explicit Scope(const g2n::LabelsRequest* r) { g2n::set_labels_request(r); }
+    ~Scope() { g2n::set_labels_request(nullptr); }
   } scope(&req);
   return build_from_path(path, &o, res);
 }

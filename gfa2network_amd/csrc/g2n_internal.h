@@ -109,6 +109,14 @@ struct StatsRequest {
 };
 void set_stats_request(const StatsRequest* req);  // nullptr: none (thread-local)
 
+// g2n_components_from_path: the same build with its names kept whole; g2n_csr_components labels the
+// CSR on the device, and the labels (the result's rows: int32, one per node) and the names come back.
+struct LabelsRequest {
+  g2n_components_info* info;
+  bool check_ascii;  // as StatsRequest::check_ascii
+};
+void set_labels_request(const LabelsRequest* req);  // nullptr: none (thread-local)
+
 // g2n_graph_gexf_from_path / _from_buffer: while set on the calling thread, a G2N_OUT_GRAPH_GEXF build opens
 // its document with these bytes (host; the XML declaration through </meta>, a newline behind it).
 struct GexfHead {
@@ -212,5 +220,8 @@ int write_npz(const std::string& path, int n, const char* const* names, const ui
               const uint64_t* head_lens, const void* const* datas, const uint64_t* data_lens, int level);
 int write_node_map(const std::string& path, const uint8_t* blob, const int64_t* offs, uint64_t n);
 int64_t first_bad_utf8(const uint8_t* blob, const int64_t* offs, uint64_t n);
+// "name\tlabel\n" per node (the components CLI's listing); path "-": standard output
+int write_node_labels(const std::string& path, const uint8_t* blob, const int64_t* offs, const int32_t* labels,
+                      uint64_t n);
 
 }  // namespace g2n

@@ -29,6 +29,7 @@
 #include "g2n_inflate.hip"
 #include "g2n_keyset.hip"
 #include "g2n_stats.hip"
+#include "g2n_components.hip"
 #include "g2n_dist.hip"
 #include "g2n_wdist.hip"
 #include "g2n_pairs.hip"
@@ -53,6 +54,8 @@ enum Slot {
   S_PCNT, S_POFF, S_PGRP, S_BSTART, S_SCANST, S_RBOUND, S_ROWSP, S_COLSP, S_TLEAN, S_ZIN, S_ZMEM, S_ZBAD, S_RSK, S_RSV, S_RSCNT, S_RSOFF,
   S_GCNT, S_TCN, S_INDPTR64, S_INDICES64, S_WENC, S_W1, S_W2, S_TVAL, S_PW0, S_PW1, S_BSTARTA, S_DIRECT, S_RTOT, S_SCANST2, S_EWP, S_TLIST, S_TNB, S_WENCP,
   S_STPARENT, S_STCOL, S_STDIAG, S_STLONG, S_STOUT, S_STIP, S_STIX,  // g2n_csr_stats (g2n_stats.hip)
+  S_CCFLAG, S_CCRANK, S_CCTOTAL, S_CCLABEL, S_CCIDX, S_CCKEY, S_CCPERM, S_CCPERM64, S_CCOFF, S_CCLOCAL, S_CCLEN, S_CCPOS,
+  S_CCVAL, S_CCOIP, S_CCOIX, S_CCOVAL, S_CCQUEUES,  // g2n_csr_components / g2n_csr_split_components_host (g2n_components.hip)
   S_DSEEN, S_DNEXT, S_DQUEUE, S_DQMASK, S_DLONG, S_DSTATE, S_DCNT, S_DMPTR, S_DCUR, S_DMPATH, S_DSPATH, S_DDONE,
   S_DTAB, S_DPP, S_DPN,  // g2n_csr_path_distances (g2n_dist.hip)
   S_WDIST, S_WVAL,  // g2n_csr_path_distances_weighted (g2n_wdist.hip)
@@ -2422,6 +2425,8 @@ namespace g2n {
 static void host_result(g2n_context* c, const g2n_result& D, HostResult* H, const uint8_t* in, uint64_t len) {
   if (t_stats_request)
     stats_result(c, D, H, *t_stats_request);
+  else if (t_labels_request)
+    labels_result(c, D, H, *t_labels_request);
   else if (t_dist_request)
     dist_result(c, D, H, *t_dist_request);
   else if (t_seq_request)
@@ -3301,6 +3306,31 @@ int g2n_csr_stats_host(const void* indptr, const void* indices, int32_t index_wi
   if (!out) return G2N_E_ARG;
   return g2n::guarded(
       [&] { return g2n::csr_stats_host(indptr, indices, index_width, n, nnz, directed, device, out); });
+}
+
+int g2n_csr_components(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width, uint64_t n,
+                       uint64_t nnz, int32_t* d_labels, g2n_components_info* info) {
+  if (!info) return G2N_E_ARG;
+  G2N_CTX_CALL(ctx, g2n::csr_components(ctx, "g2n_csr_components", d_indptr, d_indices, index_width, n, nnz, d_labels, info));
+  return G2N_OK;
+}
+
+int g2n_csr_components_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                            int32_t* labels, int32_t device, g2n_components_info* info) {
+  if (!info) return G2N_E_ARG;
+  return g2n::guarded(
+      [&] { return g2n::csr_components_host(indptr, indices, index_width, n, nnz, labels, device, info); });
+}
+
+int g2n_csr_split_components_host(const void* indptr, const void* indices, const void* data, int32_t value_bytes,
+                                  int32_t index_width, uint64_t n, uint64_t nnz, int32_t* labels, int64_t* perm,
+                                  int64_t* off, void* out_indptr, void* out_indices, void* out_data, int32_t device,
+                                  g2n_components_info* info) {
+  if (!info) return G2N_E_ARG;
+  return g2n::guarded([&] {
+    return g2n::csr_split_components_host(indptr, indices, data, value_bytes, index_width, n, nnz, labels, perm, off,
+                                          out_indptr, out_indices, out_data, device, info);
+  });
 }
 
 int g2n_csr_path_distances(g2n_context* ctx, const void* d_indptr, const void* d_indices, int32_t index_width, uint64_t n,

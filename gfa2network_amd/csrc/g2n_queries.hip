@@ -1,8 +1,9 @@
 // g2n_queries.hip — the queries over a finished, device-resident CSR: graph statistics
-// (g2n_csr_stats), hop distances between paths (g2n_csr_path_distances: g2n_dist.hip), weighted ones
+// (g2n_csr_stats), component labels and the matrix regrouped by component (g2n_csr_components,
+// g2n_csr_split_components_host: g2n_components.hip), hop distances between paths (g2n_csr_path_distances: g2n_dist.hip), weighted ones
 // (g2n_csr_path_distances_weighted: g2n_wdist.hip), node-to-node distances (g2n_csr_pair_distances and
 // its weighted twin: g2n_pairs.hip), and what a host build returns in place of its
-// matrix when a stats / distance / sequence-distance request is set (g2n_host.cpp).
+// matrix when a stats / labels / distance / sequence-distance request is set (g2n_host.cpp).
 //
 // Part of g2n_pipeline.hip's translation unit, included where the host results begin: it uses that
 // file's arena and stream helpers (dget, read_dev, scan_excl, shared_context, download) as they are.
@@ -201,6 +202,176 @@ int csr_stats_host(const void* indptr, const void* indices, int32_t index_width,
   return host_call(device, [&](g2n_context* c) {
     const StagedCsr d = stage_csr(c, indptr, indices, nullptr, index_width, n, nnz);
     csr_stats(c, d.indptr, d.indices, index_width, n, nnz, directed, out);
+  });
+}
+
+// ------------------------------------------------- components: labels and the split ------
+// a call's events: union-find | labels | groups | split between ev[0..4]
+
+template <class I>
+static void cc_union_t(g2n_context* c, const I* indptr, const I* indices, uint64_t n, uint64_t nnz, uint32_t* parent,
+                       StatsOut* so) {
+  const uint64_t long_cap = nnz / kStatsShortRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_STLONG, long_cap);
+  const unsigned g = grid_for(n);
+  const unsigned gr = (unsigned)std::min<uint64_t>(g, (uint64_t)c->n_cu * 8);
+  const HookOp hop{parent};
+  hipLaunchKernelGGL(k_cc_init<I>, dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, parent, so);
+  hipLaunchKernelGGL((k_rows_short<I, HookOp>), dim3(g), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop, 1,
+                     long_rows, long_cap, so);
+  hipLaunchKernelGGL((k_rows_long<I, HookOp>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, n, nnz, hop,
+                     (const uint32_t*)long_rows, long_cap, so);
+  hipLaunchKernelGGL(k_cc_flatten, dim3(gr), dim3(256), 0, c->stream, parent, n, so);
+}
+
+// The labels of a device CSR (n > 0) into d_labels (int32, n) on c's stream; returns the number of
+// components.  idx (n, or null): the identity, the sort's payload.  ev[0..2] are recorded.
+static uint64_t csr_labels(g2n_context* c, const std::string& who, const void* indptr, const void* indices,
+                           int32_t index_width, uint64_t n, uint64_t nnz, int32_t* d_labels, uint32_t* idx,
+                           StatsOut* so, hipEvent_t* ev) {
+  auto* parent = dget<uint32_t>(c, S_STPARENT, n);
+  auto* flag = dget<uint32_t>(c, S_CCFLAG, n);
+  auto* rank = dget<uint32_t>(c, S_CCRANK, n);
+  auto* total = dget<uint32_t>(c, S_CCTOTAL, 1);
+  G2N_HIP(hipEventRecord(ev[0], c->stream));
+  with_index_type(index_width, indptr, indices, [&](auto* ip, auto* ix) { cc_union_t(c, ip, ix, n, nnz, parent, so); });
+  G2N_HIP(hipEventRecord(ev[1], c->stream));
+  // the walks checked every offset and index: nothing below runs on a CSR they objected to
+  if (read_dev(c, so).bad) throw Failure(G2N_E_ARG, who + ": indptr / indices out of range");
+  const unsigned g = grid_for(n);
+  hipLaunchKernelGGL(k_cc_roots, dim3(g), dim3(256), 0, c->stream, (const uint32_t*)parent, n, flag);
+  scan_excl<uint32_t, uint32_t>(c, flag, rank, n, total);
+  hipLaunchKernelGGL(k_cc_labels, dim3(g), dim3(256), 0, c->stream, (const uint32_t*)parent, (const uint32_t*)rank, n,
+                     d_labels, idx);
+  G2N_HIP(hipEventRecord(ev[2], c->stream));
+  const uint64_t k = read_dev(c, total);
+  if (k == 0 || k > n) throw Failure(G2N_E_DEVICE, who + ": component count out of range");
+  return k;
+}
+
+static void components_times(g2n_components_info* info, hipEvent_t* ev, bool split) {
+  float ms = 0.f;
+  G2N_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  info->ms_union = ms;
+  G2N_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+  info->ms_labels = ms;
+  if (!split) return;
+  G2N_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+  info->ms_group = ms;
+  G2N_HIP(hipEventElapsedTime(&ms, ev[3], ev[4]));
+  info->ms_split = ms;
+}
+
+static void csr_components(g2n_context* c, const std::string& who, const void* indptr, const void* indices,
+                           int32_t index_width, uint64_t n, uint64_t nnz, int32_t* d_labels,
+                           g2n_components_info* info) {
+  std::memset(info, 0, sizeof(*info));
+  check_csr(who, index_width, n, nnz, (!n || indptr) && (!n || d_labels), indices, true);
+  if (n == 0) return;
+  Events<5> ev;
+  ev.create();
+  StatsOut* so = stats_out_reset(c);
+  info->n_components = (int64_t)csr_labels(c, who, indptr, indices, index_width, n, nnz, d_labels, nullptr, so, ev.e);
+  components_times(info, ev.e, false);
+}
+
+int csr_components_host(const void* indptr, const void* indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                        int32_t* labels, int32_t device, g2n_components_info* info) {
+  check_csr("g2n_csr_components_host", index_width, n, nnz, indptr && (!n || labels), indices, false);
+  return host_call(device, [&](g2n_context* c) {
+    const StagedCsr d = stage_csr(c, indptr, indices, nullptr, index_width, n, nnz);
+    auto* dl = dget<int32_t>(c, S_CCLABEL, n);
+    csr_components(c, "g2n_csr_components_host", d.indptr, d.indices, index_width, n, nnz, dl, info);
+    if (n) G2N_HIP(hipMemcpyAsync(labels, dl, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+template <class I, int VB>
+static void split_copy_t(g2n_context* c, const I* indptr, const I* indices, const void* data, uint64_t n, uint64_t nnz,
+                         const uint32_t* perm, const uint32_t* local, const int64_t* pos, void* out_indptr,
+                         void* out_indices, void* out_data, StatsOut* so) {
+  // the queues of longer rows: at most nnz / kSplitShortRow of them, of which nnz / kSplitHugeRow past the block's share
+  const uint64_t long_cap = nnz / kSplitShortRow + 1, huge_cap = nnz / kSplitHugeRow + 1;
+  auto* long_rows = dget<uint32_t>(c, S_STLONG, long_cap + huge_cap);
+  uint32_t* huge_rows = long_rows + long_cap;
+  auto* sq = dget<SplitQueues>(c, S_CCQUEUES, 1);
+  G2N_HIP(hipMemsetAsync(sq, 0, sizeof(SplitQueues), c->stream));
+  hipLaunchKernelGGL((k_split_short<I, VB>), dim3(grid_for(n + 1)), dim3(256), 0, c->stream, indptr, indices, data, n, nnz,
+                     perm, local, pos, (I*)out_indptr, (I*)out_indices, out_data, long_rows, long_cap, huge_rows, huge_cap,
+                     sq, so);
+  hipLaunchKernelGGL((k_split_long<I, VB>), dim3(kStatsLongBlocks), dim3(256), 0, c->stream, indptr, indices, data, n, nnz,
+                     perm, local, pos, (I*)out_indices, out_data, (const uint32_t*)long_rows, long_cap,
+                     (const uint32_t*)huge_rows, huge_cap, (const SplitQueues*)sq, so);
+}
+
+int csr_split_components_host(const void* indptr, const void* indices, const void* data, int32_t value_bytes,
+                              int32_t index_width, uint64_t n, uint64_t nnz, int32_t* labels, int64_t* perm, int64_t* off,
+                              void* out_indptr, void* out_indices, void* out_data, int32_t device,
+                              g2n_components_info* info) {
+  const std::string who = "g2n_csr_split_components_host";
+  std::memset(info, 0, sizeof(*info));
+  if (value_bytes != 0 && value_bytes != 1 && value_bytes != 4 && value_bytes != 8)
+    throw Failure(G2N_E_ARG, who + ": value_bytes must be 0, 1, 4 or 8");
+  check_csr(who, index_width, n, nnz, indptr && off && out_indptr && (!n || (labels && perm)),
+            indices && out_indices && (!value_bytes || (data && out_data)), true);
+  if (n == 0) {
+    off[0] = 0;
+    std::memset(out_indptr, 0, (size_t)index_width);
+    return G2N_OK;
+  }
+  return host_call(device, [&](g2n_context* c) {
+    const size_t w = (size_t)index_width, vb = (size_t)value_bytes;
+    const StagedCsr d = stage_csr(c, indptr, indices, nullptr, index_width, n, nnz);
+    void* dval = vb ? dbuf(c, S_CCVAL, (size_t)nnz * vb) : nullptr;
+    if (vb && nnz) G2N_HIP(hipMemcpyAsync(dval, data, (size_t)nnz * vb, hipMemcpyHostToDevice, c->stream));
+    auto* dl = dget<int32_t>(c, S_CCLABEL, n);
+    auto* idx = dget<uint32_t>(c, S_CCIDX, n);
+    Events<5> ev;
+    ev.create();
+    StatsOut* so = stats_out_reset(c);
+    const uint64_t k = csr_labels(c, who, d.indptr, d.indices, index_width, n, nnz, dl, idx, so, ev.e);
+    info->n_components = (int64_t)k;
+    // ---- groups: the nodes ordered by label, each label's first position
+    auto* key_s = dget<uint32_t>(c, S_CCKEY, n);
+    auto* dperm = dget<uint32_t>(c, S_CCPERM, n);
+    auto* doff = dget<int64_t>(c, S_CCOFF, k + 1);
+    sort_pairs_u32<uint32_t>(c, (const uint32_t*)dl, key_s, idx, dperm, n, bits_for(k));
+    hipLaunchKernelGGL(k_cc_bounds, dim3(grid_for(n)), dim3(256), 0, c->stream, (const uint32_t*)key_s, n, k, doff);
+    G2N_HIP(hipEventRecord(ev.e[3], c->stream));
+    // ---- split: new row starts, then the copy
+    auto* local = dget<uint32_t>(c, S_CCLOCAL, n);
+    auto* len = dget<int64_t>(c, S_CCLEN, n + 1);
+    auto* pos = dget<int64_t>(c, S_CCPOS, n + 1);
+    auto* perm64 = dget<int64_t>(c, S_CCPERM64, n);
+    void* oip = dbuf(c, S_CCOIP, (size_t)(n + 1) * w);
+    void* oix = dbuf(c, S_CCOIX, (size_t)nnz * w);
+    void* oval = vb ? dbuf(c, S_CCOVAL, (size_t)nnz * vb) : nullptr;
+    with_index_type(index_width, d.indptr, d.indices, [&](auto* ip, auto* ix) {
+      using I = std::remove_cv_t<std::remove_pointer_t<decltype(ip)>>;
+      hipLaunchKernelGGL(k_split_rows<I>, dim3(grid_for(n + 1)), dim3(256), 0, c->stream, ip, n, nnz,
+                         (const uint32_t*)dperm, (const uint32_t*)key_s, (const int64_t*)doff, k, local, len, perm64, so);
+      excl_scan<int64_t>(c, len, pos, n + 1);
+      const auto copy = [&](auto vbc) {
+        split_copy_t<I, decltype(vbc)::value>(c, ip, ix, dval, n, nnz, dperm, local, pos, oip, oix, oval, so);
+      };
+      switch (value_bytes) {
+        case 0: copy(std::integral_constant<int, 0>{}); break;
+        case 1: copy(std::integral_constant<int, 1>{}); break;
+        case 4: copy(std::integral_constant<int, 4>{}); break;
+        default: copy(std::integral_constant<int, 8>{}); break;
+      }
+    });
+    G2N_HIP(hipEventRecord(ev.e[4], c->stream));
+    if (read_dev(c, so).bad) throw Failure(G2N_E_DEVICE, who + ": the split addressed out of range");
+    G2N_HIP(hipMemcpyAsync(labels, dl, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipMemcpyAsync(perm, perm64, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipMemcpyAsync(off, doff, (size_t)(k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipMemcpyAsync(out_indptr, oip, (size_t)(n + 1) * w, hipMemcpyDeviceToHost, c->stream));
+    if (nnz) G2N_HIP(hipMemcpyAsync(out_indices, oix, (size_t)nnz * w, hipMemcpyDeviceToHost, c->stream));
+    if (nnz && vb) G2N_HIP(hipMemcpyAsync(out_data, oval, (size_t)nnz * vb, hipMemcpyDeviceToHost, c->stream));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+    components_times(info, ev.e, true);
   });
 }
 
@@ -870,6 +1041,8 @@ int csr_pair_distances_weighted_host(const void* indptr, const void* indices, in
 // ------------------------------------------- a host build's result for a request ------
 static thread_local const StatsRequest* t_stats_request = nullptr;
 void set_stats_request(const StatsRequest* req) { t_stats_request = req; }
+static thread_local const LabelsRequest* t_labels_request = nullptr;
+void set_labels_request(const LabelsRequest* req) { t_labels_request = req; }
 static thread_local const DistRequest* t_dist_request = nullptr;
 void set_dist_request(const DistRequest* req) { t_dist_request = req; }
 static thread_local const SeqRequest* t_seq_request = nullptr;
@@ -937,6 +1110,29 @@ static void stats_result(g2n_context* c, const g2n_result& D, HostResult* H, con
   csr_stats(c, D.indptr, D.indices, D.index_width, (uint64_t)D.n_nodes, (uint64_t)D.nnz, q.directed, q.out);
   *q.n_paths = D.n_records - D.n_edges - (int64_t)c->last_n_segs;
   if (q.check_ascii) (void)ascii_key_check(c, D, H);
+}
+
+// A labels build's result (g2n_components_from_path): D's CSR stays on the device and is labelled
+// there; H receives D's scalars, the labels (r.rows: int32, one per node) and the names.
+static void labels_result(g2n_context* c, const g2n_result& D, HostResult* H, const LabelsRequest& q) {
+  scalars_result(c, D, H);
+  if (D.status != G2N_OK) return;
+  if (D.format != G2N_FMT_CSR) throw Failure(G2N_E_ARG, "g2n_components_from_path: the build returned no CSR");
+  const uint64_t n = (uint64_t)D.n_nodes;
+  if (n && (!D.names_blob || !D.names_offsets)) throw Failure(G2N_E_DEVICE, "g2n_components_from_path: no names");
+  if (q.check_ascii && ascii_key_check(c, D, H)) return;
+  g2n_result& R = H->r;
+  auto* dl = dget<int32_t>(c, S_CCLABEL, n);
+  csr_components(c, "g2n_components_from_path", D.indptr, D.indices, D.index_width, n, (uint64_t)D.nnz, dl, q.info);
+  R.rows = download(c, H->rows, dl, (size_t)n * 4);
+  if (n) {
+    const int64_t* offs = (const int64_t*)download(c, H->offs, D.names_offsets, (size_t)(n + 1) * sizeof(int64_t));
+    G2N_HIP(hipStreamSynchronize(c->stream));
+    R.names_blob = (const uint8_t*)download(c, H->blob, D.names_blob, (size_t)offs[n]);
+    R.names_offsets = offs;
+    R.names_bytes = D.names_bytes;
+  }
+  G2N_HIP(hipStreamSynchronize(c->stream));
 }
 
 // What a distance or sequence-distance build's result begins with: H receives D's scalars; false = the

@@ -9,6 +9,8 @@
 //     piece CRCs are combined with crc32_combine.
 //   * nodes.tsv: "i\tname\n" per node id, formatted per 1M-name range on its own thread and
 //     written with pwrite at offsets from a prefix sum of the line lengths.
+//   * the components CLI's "name\tlabel\n" per node (g2n_write_node_labels): ranges formatted on
+//     host threads a round at a time and written in order, so the target may be a pipe.
 #include <errno.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -322,4 +324,73 @@ int write_node_map(const std::string& path, const uint8_t* blob, const int64_t* 
   return G2N_OK;
 }
 
+int write_node_labels(const std::string& path, const uint8_t* blob, const int64_t* offs, const int32_t* labels,
+                      uint64_t n) {
+  const bool to_stdout = path == "-";
+  const int fd = to_stdout ? 1 : ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+  if (fd < 0) throw Failure(G2N_E_IO, path + ": " + std::strerror(errno));
+  struct Closer {
+    int fd;
+    ~Closer() {
+      if (fd != 1) ::close(fd);
+    }
+  } closer{fd};
+  const uint64_t chunk = 1 << 18;
+  const size_t nch = (size_t)((n + chunk - 1) / chunk);
+  const size_t T = (size_t)std::max(1, host_threads());
+  std::vector<std::vector<uint8_t>> bufs(std::min(T, nch));
+  for (size_t c0 = 0; c0 < nch; c0 += T) {  // a round: T ranges formatted side by side, written in order
+    const size_t cn = std::min(T, nch - c0);
+    parallel_for(cn, (int)T, [&](size_t k) {
+      const uint64_t lo = (c0 + k) * chunk, hi = std::min<uint64_t>(n, lo + chunk);
+      size_t bytes = (size_t)(offs[hi] - offs[lo]) + 2 * (size_t)(hi - lo);
+      for (uint64_t i = lo; i < hi; i++) bytes += labels[i] < 0 ? 11 : digits((uint64_t)labels[i]);
+      std::vector<uint8_t>& buf = bufs[k];
+      buf.resize(bytes);
+      uint8_t* d = buf.data();
+      char num[24];
+      for (uint64_t i = lo; i < hi; i++) {
+        const size_t len = (size_t)(offs[i + 1] - offs[i]);
+        if (len) std::memcpy(d, blob + offs[i], len);
+        d += len;
+        *d++ = '\t';
+        int64_t v = labels[i];
+        if (v < 0) {
+          *d++ = '-';
+          v = -v;
+        }
+        uint32_t q = 0;
+        do {
+          num[q++] = (char)('0' + v % 10);
+          v /= 10;
+        } while (v);
+        while (q) *d++ = (uint8_t)num[--q];
+        *d++ = '\n';
+      }
+      buf.resize((size_t)(d - buf.data()));
+    });
+    for (size_t k = 0; k < cn; k++) write_all(fd, bufs[k].data(), bufs[k].size(), to_stdout ? "<stdout>" : path);
+  }
+  return G2N_OK;
+}
+
 }  // namespace g2n
+
+extern "C" int g2n_write_node_labels(const char* path, const uint8_t* blob, const int64_t* offsets,
+                                     const int32_t* labels, uint64_t n_names, int32_t check_utf8, int64_t* bad_index) {
+  if (!path || (n_names && (!offsets || !labels))) return G2N_E_ARG;
+  if (bad_index) *bad_index = -1;
+  return g2n::guarded([&]() -> int {
+    static const uint8_t none = 0;
+    if (!blob) blob = &none;  // every name empty
+    uint64_t n = n_names;
+    if (check_utf8 && n_names) {
+      const int64_t bad = g2n::first_bad_utf8(blob, offsets, n_names);
+      if (bad >= 0) {
+        n = (uint64_t)bad;
+        if (bad_index) *bad_index = bad;
+      }
+    }
+    return g2n::write_node_labels(path, blob, offsets, labels, n);
+  });
+}

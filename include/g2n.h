@@ -327,6 +327,12 @@ int g2n_write_npz(const char *path, int32_t n_members, const char *const *names,
 int g2n_write_node_map(const char *path, const uint8_t *blob, const int64_t *offsets, uint64_t n_names,
                        int32_t check_utf8, int64_t *bad_index);
 
+/* The components CLI's listing: "name\tlabel\n" for the names blob/offsets in id order, labels[i] the
+ * int32 label of node i.  path "-" writes to standard output (the ranges are written in order, so
+ * the target may be a pipe).  check_utf8 and *bad_index as g2n_write_node_map's. */
+int g2n_write_node_labels(const char *path, const uint8_t *blob, const int64_t *offsets, const int32_t *labels,
+                          uint64_t n_names, int32_t check_utf8, int64_t *bad_index);
+
 /* Index of the first name that is not valid UTF-8 (Python's strict decoder), or -1. */
 int64_t g2n_first_bad_utf8(const uint8_t *blob, const int64_t *offsets, uint64_t n_names);
 
@@ -582,6 +588,57 @@ int g2n_csr_stats_host(const void *indptr, const void *indices, int32_t index_wi
  * key (whose .decode("ascii") raises the reference's error). */
 int g2n_stats_from_path(const char *path, const g2n_options *opts, g2n_graph_stats *out, int64_t *n_paths,
                         g2n_result **res);
+
+/* ---- connected components: node labels and the matrix regrouped by component (extension) ----------
+ * Every stored (u, v) joins u and v; the values are never read.  labels[i] (int32) is the number of
+ * i's component, components numbered by their smallest node index — the numbering of
+ * scipy.sparse.csgraph.connected_components(A, directed=False), and of
+ * enumerate(nx.connected_components(G.to_undirected())) for node ids in first-touch order.  The
+ * union-find is g2n_csr_stats'; its roots are the components' smallest indices however the races go,
+ * so the labels are the same on every run.  ms_*: hipEvent times of the kernel groups (the union-find,
+ * the labels; the split's sort and bounds, its row starts and copy — 0 for a labels call). */
+typedef struct g2n_components_info {
+  int64_t n_components;
+  double ms_union, ms_labels, ms_group, ms_split; /* hipEvent, pipeline stream */
+} g2n_components_info;
+
+/* d_indptr (n + 1) / d_indices (nnz) / d_labels (n, out): DEVICE pointers on ctx's device; sizes,
+ * limits and G2N_E_ARG for a bad indptr / indices as g2n_csr_stats (nothing out of range is ever
+ * addressed).  n = 0: no component. */
+int g2n_csr_components(g2n_context *ctx, const void *d_indptr, const void *d_indices, int32_t index_width, uint64_t n,
+                       uint64_t nnz, int32_t *d_labels, g2n_components_info *info);
+
+/* The same for a CSR in HOST memory: labels (n, out) is host memory too. */
+int g2n_csr_components_host(const void *indptr, const void *indices, int32_t index_width, uint64_t n, uint64_t nnz,
+                            int32_t *labels, int32_t device, g2n_components_info *info);
+
+/* The matrix regrouped by component, for a CSR in HOST memory with optional values (data: nnz items
+ * of value_bytes 1, 4 or 8 bytes, copied as bits; value_bytes 0: none, data / out_data unread).  The
+ * caller allocates every output:
+ *   labels[n]          as above
+ *   perm[n]            the nodes ordered by label, index order kept inside a component (numpy's
+ *                      argsort(labels, kind="stable"))
+ *   off[n + 1]         the first k + 1 are written (k = info->n_components <= n): component j's nodes
+ *                      are perm[off[j] .. off[j + 1]), off[k] = n
+ *   out_indptr[n + 1], out_indices[nnz], out_data[nnz]   (index_width / value_bytes as the input)
+ *                      row p is the input's row perm[p], its entries in their stored order, each
+ *                      column replaced by its node's index inside its own component.  Both ends of
+ *                      a stored entry are in one component, so this is a permutation of the whole
+ *                      matrix and component j is rows [off[j], off[j + 1]) of it: a CSR of its own
+ *                      once out_indptr is rebased by out_indptr[off[j]].
+ * Rows up to 64 entries are copied by a thread each, up to 4096 by a block each, longer ones by the
+ * whole grid. */
+int g2n_csr_split_components_host(const void *indptr, const void *indices, const void *data, int32_t value_bytes,
+                                  int32_t index_width, uint64_t n, uint64_t nnz, int32_t *labels, int64_t *perm,
+                                  int64_t *off, void *out_indptr, void *out_indices, void *out_data, int32_t device,
+                                  g2n_components_info *info);
+
+/* The labels of the graph compute_stats measures: ingest, build, options read, errors, the one-shot
+ * warning and the ASCII key check (want_node_names = 1; 0 = raw_bytes_id) are g2n_stats_from_path's.
+ * The CSR stays on the device and g2n_csr_components runs on it there.  On G2N_OK *res carries the
+ * labels in `rows` (int32, n_nodes of them; no other matrix field is set) and the names
+ * (names_blob / names_offsets) whatever want_node_names says. */
+int g2n_components_from_path(const char *path, const g2n_options *opts, g2n_components_info *info, g2n_result **res);
 
 /* ---- path distances (gfa2network/analysis.py genome_distance_matrix) ---------------------------
  * Hop distances between K node lists ("paths") over a CSR's structure: every stored (u, v) is an
