@@ -2235,7 +2235,9 @@ __device__ __forceinline__ void lean_tile(const uint8_t* __restrict__ in, uint64
         const uint32_t o = 16 * c0 + (uint32_t)__builtin_ctzll(m);
         m &= m - 1;
         const uint32_t code = q < kLeanBatch ? (codes >> (2 * q)) & 3u : lean_code(kind_at(buf, o, t0 + o, len));
-        if (w0 == 0 && code == 1 && ep) is.fail = 1;  // an S line after an edge line: not the decimal-id layout
+        // an S line after an edge line of the tile: not the decimal-id / S-first layout.  Checked in every window:
+        // window 0 stops at rank kLeanLines, and a later window walks the thread's starts again from its first
+        if (code == 1 && ep) is.fail = 1;
         if (r >= w0) rec[r - w0] = o | (code << 15) | ((code == 1 ? sp : ep) << 17);
         sp += code == 1;
         ep += code == 2;
