@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "g2n_kernels.h"
+#include "decfmt.h"
 #include "g2n_scan.hip"
 #include "pylit.h"
 #include "stl_sort.h"
@@ -2938,24 +2939,7 @@ __global__ void __launch_bounds__(kTPB) k_names_lean_bidir(const uint8_t* __rest
 // Names of a decimal-id build (the premise held: S line k names "k+1", S lines first): node id's
 // key is str(k + 1) (bidirected: id = 2k + [ori == '-'], key str(k + 1) + ":+" / ":-"), so the
 // names blob and its offsets are arithmetic — no key lengths, scan or gathers from the input.
-__device__ __host__ inline uint32_t dec_digits(uint64_t v) {
-  uint32_t d = 1;
-  for (uint64_t p = 10; v >= p && d < 20; p *= 10) d++;
-  return d;
-}
-__device__ __host__ inline uint64_t dec_digits_upto(uint64_t v) {  // sum of dec_digits(k), k = 1..v
-  uint64_t s = 0, lo = 1;
-  for (uint32_t d = 1; lo <= v && d < 20; d++, lo *= 10) {
-    const uint64_t hi = lo * 10 - 1, top = v < hi ? v : hi;
-    s += (top - lo + 1) * d;
-  }
-  return s;
-}
-__device__ __host__ inline uint64_t dec_name_off(uint64_t id, int bidir) {  // offset of node id's key
-  if (!bidir) return dec_digits_upto(id);
-  const uint64_t k = id >> 1;
-  return 2 * (dec_digits_upto(k) + 2 * k) + ((id & 1) ? dec_digits(k + 1) + 2 : 0);
-}
+// (dec_digits, dec_digits_upto, dec_name_off: decfmt.h)
 
 // node k's key str(k + 1) (bidirected: + ":+" / ":-"), byte stores.  It runs on the side stream beside
 // F1, so what counts is what it takes from F1 (0.2-0.3 ms of F1's time on C4).  Measured dead ends
@@ -4028,25 +4012,11 @@ __global__ void __launch_bounds__(kTPB) k_edge_text(const int32_t* __restrict__ 
 // each block's kTextEdges line lengths; after a scan of those block sums k_edge_dec_text recomputes
 // them, scans them inside the block and renders the block's lines in LDS (at most 1024 x 26 bytes:
 // two 10-digit keys, ":o" twice, tab and newline), then writes them with aligned 16-byte stores.
-// Algorithmic bytes per edge: 8 read twice + the line written.  The digit work is VALU and sets the
-// render's pace: a key's digit count is clz-based (one LDS table read, no compare chain), its digits
-// come four at a time by SWAR (a 4-digit value split into 2-digit then 1-digit byte lanes by
-// multiply-shift: x / 100 = (x * 5243) >> 19 for x < 10^4, x / 10 = (x * 103) >> 10 for x < 100; no
-// carry crosses a lane).
-__device__ inline uint32_t dec4_ascii(uint32_t y) {  // y < 10^4: its 4 digits, most significant in byte 0
-  const uint32_t h = (y * 5243u) >> 19;
-  uint32_t z = h | ((y - h * 100u) << 16);
-  const uint32_t t = ((z * 103u) >> 10) & 0x000F000Fu;
-  z = t | ((z - t * 10u) << 8);
-  return z | 0x30303030u;
-}
+// Algorithmic bytes per edge: 8 read twice + the line written.  The digit arithmetic (dec_ndig, dec4_ascii,
+// dec_key_put) is decfmt.h, host+device.
 struct DecKeys {  // a thread's kDecPer edges: the two keys' values (id + 1, bidirected id / 2 + 1) and digits
   uint32_t va[4], vb[4], na[4], nb[4], l[4];  // l: line length (0: past the end)
 };
-__device__ inline uint32_t dec_ndig(uint32_t v, const uint32_t* p10 /* LDS: 10^0 .. 10^9 */) {  // v >= 1
-  const uint32_t t = ((32u - (uint32_t)__clz(v)) * 1233u) >> 12;  // log10(2^bits), 0..9
-  return t + (v >= p10[t] ? 1u : 0u);
-}
 __device__ inline void dec_p10(uint32_t* p10) {
   if (threadIdx.x < 10) {
     uint32_t p = 1;
@@ -4054,28 +4024,6 @@ __device__ inline void dec_p10(uint32_t* p10) {
     p10[threadIdx.x] = p;
   }
   __syncthreads();
-}
-// the key of value v (n digits) at d, plus ":+" / ":-" when bidirected; returns the byte after it.
-// (Writing every key as 8 zero-padded bytes back to front, without per-byte predicates, measured the
-// same 1.19 ms on C4: the render runs at ~4.3 TB/s of ids read + text written.)
-__device__ inline uint8_t* dec_key_put(uint8_t* d, uint32_t v, uint32_t n, int bidir, uint32_t id) {
-  if (n > 8) {  // the leading 1-2 digits, then the low 8
-    const uint32_t hi = v / 100000000u;
-    v -= hi * 100000000u;
-    if (hi > 9) *d++ = (uint8_t)('0' + hi / 10u);
-    *d++ = (uint8_t)('0' + hi % 10u);
-    n = 8;
-  }
-  const uint32_t a = v / 10000u;
-  const uint64_t w = (((uint64_t)dec4_ascii(v - a * 10000u) << 32) | dec4_ascii(a)) >> (8u * (8u - n));
-  for (uint32_t j = 0; j < n; j++) d[j] = (uint8_t)(w >> (8u * j));
-  d += n;
-  if (bidir) {
-    d[0] = ':';
-    d[1] = (id & 1u) ? '-' : '+';
-    d += 2;
-  }
-  return d;
 }
 constexpr uint32_t kDecPer = kTextEdges / kTPB;  // edges per thread (4), consecutive
 static_assert(kDecPer == 4 && kTextEdges * 26u + 16u <= kTextLds, "a block's lines fit the LDS stage");

@@ -3,7 +3,9 @@ libstdc++ themselves.
 
 * pylit.h (the GPU's copy of CPython int()/float() literal semantics) vs int()/float();
 * stl_sort.h (the GPU's restatement of libstdc++ std::sort) vs std::sort, including the
-  heap-sort fallback the introsort depth limit triggers.
+  heap-sort fallback the introsort depth limit triggers;
+* decfmt.h (the digit arithmetic of a decimal-id build's names and edge-list text) vs snprintf and
+  str(): the compare loops are C++ (hostcheck.cpp) and return the first value that differs.
 """
 import ctypes
 import decimal
@@ -28,6 +30,11 @@ def hc(tmp_path_factory):
     for f in ("hc_py_float", "hc_py_int", "hc_fast_int", "hc_fast_float", "hc_utf8_valid"):
         getattr(lib, f).restype = ctypes.c_int
     lib.hc_sort_both.restype = None
+    u64 = ctypes.c_uint64
+    lib.hc_dec_key_range.restype, lib.hc_dec_key_range.argtypes = u64, [u64, u64, u64]
+    lib.hc_dec_key_list.restype, lib.hc_dec_key_list.argtypes = u64, [ctypes.c_void_p, ctypes.c_int64]
+    lib.hc_dec_name_off.restype, lib.hc_dec_name_off.argtypes = u64, [u64, ctypes.c_int]
+    lib.hc_dec_name_off_run.restype, lib.hc_dec_name_off_run.argtypes = ctypes.c_int64, [u64, ctypes.c_int]
     return lib
 
 
@@ -180,3 +187,61 @@ def test_stl_sort_depth_limit_fallback(hc):
         organ = np.concatenate([np.arange(n // 2), np.arange(n // 2)[::-1]]).astype(np.int32)
         a, b = _sort_both(hc, organ)
         assert np.array_equal(a, b)
+
+
+V_MAX = 2 ** 31 - 1  # node ids are below 2^31; a key's value is id + 1 (bidirected: id / 2 + 1)
+
+
+def test_dec_key_every_value_to_10_7(hc):
+    """dec_ndig, dec_digits and dec_key_put (plain, bidirected, both id parities) against snprintf."""
+    assert hc.hc_dec_key_range(1, 10 ** 7, 1) == 0
+
+
+def test_dec_key_around_powers_of_ten_and_two(hc):
+    """Every value within 10^4 of a power of ten or of two below 2^31 (where the digit count, the clz estimate,
+    the low / high half and the 9- and 10-digit branch step), and 1 + 9973 j up to 2^31 - 1."""
+    for p in [10 ** k for k in range(10)] + [2 ** j for j in range(32)]:
+        lo, hi = max(1, p - 10 ** 4), min(V_MAX, p + 10 ** 4)
+        if lo <= hi:
+            assert hc.hc_dec_key_range(lo, hi, 1) == 0, p
+    assert hc.hc_dec_key_range(1, V_MAX, 9973) == 0
+
+
+def test_dec_key_every_high_half(hc):
+    """hi * 10^8 + a * 10^4 + (37 a mod 10^4) for hi in {0, 1, 9, 10, 21} and every a < 10^4, below 2^31: every
+    value of dec_key_put's `a` half beside a varying low half, without and with the leading 1 - 2 digits."""
+    a = np.arange(10 ** 4, dtype=np.int64)
+    for hi in (0, 1, 9, 10, 21):
+        v = hi * 10 ** 8 + a * 10 ** 4 + (37 * a) % 10 ** 4
+        v = np.ascontiguousarray(v[(v >= 1) & (v <= V_MAX)], dtype=np.uint32)
+        assert len(v) >= (4748 if hi == 21 else 9999), hi
+        assert hc.hc_dec_key_list(v.ctypes.data, len(v)) == 0, hi
+    # the compare itself: a few values against Python's str through the same entry points
+    for v in (1, 9, 10, 99999, 100000, 99999999, 100000000, 999999999, 1000000000, V_MAX):
+        one = np.array([v], dtype=np.uint32)
+        assert hc.hc_dec_key_list(one.ctypes.data, 1) == 0, v
+
+
+def _name_off(i, bidir):
+    """The offset of node i's key: the summed lengths of the keys before it, by digit-count groups."""
+    def upto(v):  # sum of len(str(k)), k = 1 .. v
+        return sum(d * (min(v, 10 ** d - 1) - 10 ** (d - 1) + 1) for d in range(1, len(str(v)) + 1)) if v else 0
+    if not bidir:
+        return upto(i)
+    k = i >> 1
+    return 2 * (upto(k) + 2 * k) + ((len(str(k + 1)) + 2) if i & 1 else 0)
+
+
+def test_dec_name_off(hc):
+    """dec_name_off against the running sum of the keys' lengths for ids up to 2 * 10^7, and against the closed
+    form at 10^k, 10^k +- 1 (the ids whose key gains a digit) up to 2^31 - 2, plain and bidirected."""
+    assert [_name_off(i, 0) for i in (0, 1, 9, 10, 11)] == [0, 1, 9, 11, 13]
+    assert [_name_off(i, 1) for i in (0, 1, 2, 3, 18, 19, 20)] == [0, 3, 6, 9, 54, 58, 62]
+    for bidir in (0, 1):
+        assert hc.hc_dec_name_off_run(2 * 10 ** 7, bidir) == -1, bidir
+        ids = {0, 1, 2, 2 ** 31 - 2, 2 ** 31 - 3}
+        for k in range(1, 10):
+            for m in (1, 2):  # (bidirected: id 2 (10^k - 1) is the first of 10^k's two keys)
+                ids |= {m * 10 ** k + d for d in (-3, -2, -1, 0, 1, 2, 3)}
+        for i in sorted(x for x in ids if 0 <= x <= 2 ** 31 - 2):
+            assert hc.hc_dec_name_off(i, bidir) == _name_off(i, bidir), (i, bidir)
